@@ -29,7 +29,12 @@ Execution: the step is captured once in HIP graph(s) and replayed (`--no-graph`:
 At N=1 the measurement runs in a child process; if it dies the parent re-measures (linear graph, then eager launches), so
 a bench line is always produced; `attempts` in the JSON records what happened.
 
-Extra legs (rank 0, after the timed region, not part of `value`):
+A plain run times the headline only.  `--full` adds the extra legs below (each one's count option can also be given by itself).
+`--dump-outputs DIR` writes what the LAST timed step handed its caller (loss, loss terms, model outputs, a seeded sample and the
+norms of the parameter gradients) as DIR/<name>.npy; the inputs depend on the arguments only, so two builds compare output for output.
+
+Extra legs (`--full`; rank 0, after the timed region, not part of `value`):
+  dedupe       : `--dedupe-steps` eager steps with the slow frames not recomputed, reported as `value_dedupe`.
   roofline     : `--roofline-steps` more identical steps, launched eagerly, with HIP events recorded on the launch
                  stream around every launch of the MFMA kernel families; per family achieved = algorithmic FLOPs or
                  algorithmic HBM bytes / summed event-bracketed duration (nothing subtracted: the bracketing itself adds a
@@ -134,7 +139,8 @@ def cpu_baseline(T_sample, res, k, L, T_full):
     from oracle.tubedetr_oracle import OracleConfig, train_step
     from oracle.weights import fill_state, state_spec, synthetic_batch
 
-    cores = min(os.cpu_count() or 1, 32)  # more threads than this only slows the small-batch CPU convolutions down
+    # more than 32 threads only slows the small-batch CPU convolutions down; an OMP_NUM_THREADS quota is kept
+    cores = min(os.cpu_count() or 1, 32, int(os.environ.get("OMP_NUM_THREADS") or 32))
     torch.set_num_threads(cores)
     cfg = OracleConfig(stride=k)
     sd = fill_state(state_spec(cfg), 1, requires_grad=True)
@@ -208,7 +214,64 @@ def _load_profile_json(name):
         return {}
 
 
-def main():
+def _detached(x):
+    if torch.is_tensor(x):
+        return x.detach()
+    if isinstance(x, dict):
+        return {k_: _detached(v) for k_, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_detached(v) for v in x]
+    return x
+
+
+DUMP_ARRAY_CAP = 1 << 20  # elements per model-output array; larger ones are written as a fixed, seeded sample
+DUMP_GRAD_SAMPLE = 4096  # gradient values kept per parameter
+
+
+def dump_outputs(out_dir, returned, params):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy.  loss; term_<name> for every entry of the loss dict; out_<key> for every
+    model output, aux_<key> for the auxiliary decoder layers' outputs stacked along axis 0 (float32; an array of more than
+    DUMP_ARRAY_CAP elements is a seeded sample of its flattened values); grad_norm = every trainable parameter's gradient L2 norm
+    (float64, parameter order); grad_sample = DUMP_GRAD_SAMPLE values per parameter at seeded indices (all of a smaller one), concatenated
+    in parameter order.  The sample indices depend on the shapes only."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": returned["loss"].reshape(1)}
+    for k_, v in sorted(returned["loss_dict"].items()):
+        if torch.is_tensor(v):
+            arrays[f"term_{k_}"] = v.reshape(-1)
+    for k_, v in sorted(returned["outputs"].items()):
+        if torch.is_tensor(v):
+            arrays[f"out_{k_}"] = v
+        elif k_ == "aux_outputs" and v:
+            for kk in sorted(v[0]):
+                if torch.is_tensor(v[0][kk]):
+                    arrays[f"aux_{kk}"] = torch.stack([layer[kk] for layer in v])
+    g = torch.Generator().manual_seed(0)
+    norms, sample = [], []
+    for p_ in params:
+        gr = p_.grad.detach().reshape(-1) if p_.grad is not None else torch.zeros(p_.numel(), device=p_.device)
+        norms.append(torch.linalg.vector_norm(gr, dtype=torch.float64))
+        n = gr.numel()
+        idx = torch.arange(n) if n <= DUMP_GRAD_SAMPLE else torch.randint(0, n, (DUMP_GRAD_SAMPLE,), generator=g)
+        sample.append(gr[idx.to(gr.device)].float())
+    arrays["grad_sample"] = torch.cat(sample)
+    total = 0
+    for name, t_ in arrays.items():
+        t_ = t_.detach()
+        if t_.numel() > DUMP_ARRAY_CAP and name != "grad_sample":
+            t_ = t_.reshape(-1)[torch.randint(0, t_.numel(), (DUMP_ARRAY_CAP,), generator=g).to(t_.device)]
+        arr = t_.float().cpu().numpy()
+        total += arr.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    arr = torch.stack(norms).cpu().numpy()
+    np.save(os.path.join(out_dir, "grad_norm.npy"), arr)
+    total += arr.nbytes
+    print(f"[bench] wrote {len(arrays) + 1} arrays ({total / 2**20:.1f} MiB) to {out_dir}", file=sys.stderr, flush=True)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
@@ -216,13 +279,18 @@ def main():
     ap.add_argument("--workload", default="cfg3", choices=list(WORKLOADS))
     ap.add_argument("--clips-per-gpu", type=int, default=DEFAULT_CLIPS_PER_GPU, help="videos per GPU per step (the reference's --batch_size, main.py:63)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--roofline-steps", type=int, default=1)
-    ap.add_argument("--cpu-frames", type=int, default=100, help="frames of the CPU-baseline sample clip (0 = skip); 100 = the benchmarked clip itself: ~18 s per pass, 3 passes")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: dedupe timing, roofline and CPU baseline (their count options default to 5 / 1 / 100 "
+                         "with --full, to 0 without it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (loss, loss terms, model outputs, gradient sample and norms) as DIR/<name>.npy")
+    ap.add_argument("--roofline-steps", type=int, default=None, help="eager steps of the roofline leg (default: 1 with --full, else 0)")
+    ap.add_argument("--cpu-frames", type=int, default=None, help="frames of the CPU-baseline sample clip (0 = skip; default: 100 with --full, else 0); 100 = the benchmarked clip itself: ~18 s per pass, 3 passes")
     ap.add_argument("--keep-prepared-weights", action="store_true", help="diagnostic: reuse prepared bf16 weights across steps")
     ap.add_argument("--dedupe", action="store_true",
                     help="do not recompute the slow frames inside the fast pass (exact, slow = video[::k]); off by default so the timed step "
                          "executes the same work as the reference's")
-    ap.add_argument("--dedupe-steps", type=int, default=5, help="N=1: eager steps timed with the dead work skipped, reported as value_dedupe beside the headline (0 = skip)")
+    ap.add_argument("--dedupe-steps", type=int, default=None, help="N=1: eager steps timed with the dead work skipped, reported as value_dedupe beside the headline (0 = skip; default: 5 with --full, else 0)")
     ap.add_argument("--graph", dest="graph", action="store_true", default=True, help="capture the step in HIP graph(s)")
     ap.add_argument("--no-graph", dest="graph", action="store_false")
     ap.add_argument("--force-ddp", action="store_true", help="diagnostic: run the N>1 code path (process group + gradient exchange) with one rank")
@@ -253,7 +321,15 @@ def main():
     ap.add_argument("--no-text-stream", action="store_true",
                     help="graph mode: capture RoBERTa on the main stream (a linear graph) instead of its own stream (a forked graph branch: "
                          "its latency-bound 120-row GEMMs then overlap the trunk, ~2 ms per step at 4 clips; the default at N=1)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    for name_, full_default in (("roofline_steps", 1), ("cpu_frames", 100), ("dedupe_steps", 5)):
+        if getattr(a, name_) is None:
+            setattr(a, name_, full_default if a.full else 0)
+    return a
+
+
+def main():
+    a = parse_args()
 
     if os.environ.get("TD_EFENCE") == "1":  # diagnostic: electric-fence device allocator (tests/efence/), eager launches only
         sys.path.insert(0, os.path.join(ROOT, "tests", "efence"))
@@ -368,6 +444,11 @@ def main():
     n_batches = a.warmup + a.steps + a.roofline_steps
     batches = [make_batch(T, res, k, L, 1000 * rank + s, dev, B, a.frames) for s in range(min(n_batches, 4))]
     params = [p_ for p_ in model.parameters() if p_.requires_grad]
+    returned = {}  # --dump-outputs: what the step hands its caller (graph mode: the captured step's static tensors, rewritten by every replay)
+
+    def keep_returned(loss, loss_dict, outputs):
+        if a.dump_outputs:
+            returned.update(loss=loss.detach(), loss_dict=_detached(loss_dict), outputs=_detached(outputs))
 
     def eager_step(i):
         b = batches[i % len(batches)]
@@ -378,7 +459,8 @@ def main():
             p_.grad = None
         if reducer is not None:
             sync_num_boxes(b["target_boxes"].shape[0], criterion.external_num_boxes)
-        loss, _, _, _ = forward_step(net, criterion, weight_dict, b)
+        loss, ld_, out_, _ = forward_step(net, criterion, weight_dict, b)
+        keep_returned(loss, ld_, out_)
         if staged and pieces > 1:
             backward_in_stages(model, loss, after_first_stage=lambda: reducer.launch(early=True), after_trunk_stage=lambda k_, ws_: reducer.launch(stage=k_))
             reducer.finish(attach=True)
@@ -414,7 +496,8 @@ def main():
             def body1():
                 tok.batch = static
                 invalidate_prepared()
-                l_, _, _, _ = forward_step(net, criterion, weight_dict, static)
+                l_, ld_, out_, _ = forward_step(net, criterion, weight_dict, static)
+                keep_returned(l_, ld_, out_)
                 l_.backward()  # staged: stops at the trunk boundary
                 if reducer is not None:
                     if staged:
@@ -550,6 +633,9 @@ def main():
         torch.save({"flat": reducer.flat.detach().cpu(), "names": [n_ for n_, p_ in model.named_parameters() if p_.requires_grad],
                     "numels": [p_.numel() for p_ in reducer.params], "batch_seeds": [1000 * r_ + last for r_ in range(world)],
                     "used": reducer._global_used, "world": world}, a.dump_grads)
+    if a.dump_outputs and rank == 0:  # before the extra legs: their eager steps would overwrite the outputs and gradients
+        torch.cuda.synchronize()
+        dump_outputs(a.dump_outputs, returned, [p_ for p_ in model.parameters() if p_.requires_grad])
     assert math.isfinite(loss.item()), "non-finite loss"
 
     # ---- the same workload with the dead work skipped (`value_dedupe`): the model proves from its inputs that the slow clip is every k-th frame of

@@ -193,3 +193,54 @@ def test_roofline_families_are_named_by_kernels_of_the_committed_profile():
         for src in (traffic, mfma):
             assert key in src and src[key]["kernels"], (key, "missing from the PMC aggregate")
             assert all(k in names for k in src[key]["kernels"]), key  # exact names of the kernel-stats CSV
+
+
+def test_bench_plain_run_times_the_headline_only():
+    """`bench.py --gpus 1 --steps N --warmup W` runs no extra leg; `--full` brings back the dedupe, roofline and CPU-baseline legs with their
+    former defaults, and an explicit count wins either way."""
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.dedupe_steps, a.roofline_steps, a.cpu_frames, a.dump_outputs) == (7, 2, 0, 0, 0, None)
+    a = bench.parse_args(["--full"])
+    assert (a.dedupe_steps, a.roofline_steps, a.cpu_frames) == (5, 1, 100)
+    a = bench.parse_args(["--full", "--cpu-frames", "0", "--dump-outputs", "d"])
+    assert (a.dedupe_steps, a.roofline_steps, a.cpu_frames, a.dump_outputs) == (5, 1, 0, "d")
+    assert bench.parse_args(["--roofline-steps", "2"]).roofline_steps == 2
+
+
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files, samples large arrays at indices that depend on the shapes only, and writes the
+    same bytes for the same values."""
+    import numpy as np
+
+    import bench
+
+    g = torch.Generator().manual_seed(1)
+    params = [torch.nn.Parameter(torch.zeros(n)) for n in (10, 50_000, 3) + (bench.DUMP_GRAD_SAMPLE + 1,) * (bench.DUMP_ARRAY_CAP // bench.DUMP_GRAD_SAMPLE)]
+    for p in params:
+        p.grad = torch.randn(p.shape, generator=g)
+    params.append(torch.nn.Parameter(torch.zeros(5)))  # no gradient
+    big = torch.randn(bench.DUMP_ARRAY_CAP + 7, generator=g).to(torch.bfloat16)
+    returned = {"loss": torch.tensor(2.5), "loss_dict": {"loss_bbox": torch.tensor(0.5), "loss_giou_0": torch.tensor(1.0)},
+                "outputs": {"pred_boxes": torch.rand(6, 4, generator=g), "ca_weights": big, "pred_sted": None,
+                            "aux_outputs": [{"pred_boxes": torch.rand(6, 4, generator=g)} for _ in range(2)]}}
+    bench.dump_outputs(str(tmp_path / "a"), returned, params)
+    bench.dump_outputs(str(tmp_path / "b"), returned, params)
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == sorted(["loss.npy", "term_loss_bbox.npy", "term_loss_giou_0.npy", "out_pred_boxes.npy", "out_ca_weights.npy",
+                            "aux_pred_boxes.npy", "grad_sample.npy", "grad_norm.npy"])
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == (np.float64 if n == "grad_norm.npy" else np.float32) and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "out_ca_weights.npy").shape == (bench.DUMP_ARRAY_CAP,)
+    assert np.load(tmp_path / "a" / "aux_pred_boxes.npy").shape == (2, 6, 4)
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [2.5]
+    gs = np.load(tmp_path / "a" / "grad_sample.npy")
+    assert gs.shape == (10 + bench.DUMP_GRAD_SAMPLE + 3 + bench.DUMP_ARRAY_CAP + 5,)  # never re-sampled by the output cap
+    assert np.array_equal(gs[:10], params[0].grad.numpy()) and not gs[-5:].any()
+    norms = np.load(tmp_path / "a" / "grad_norm.npy")
+    assert np.allclose(norms[:-1], [float(p.grad.double().norm()) for p in params[:-1]]) and norms[-1] == 0

@@ -4,7 +4,7 @@
 #   1. rocprofv3 kernel stats of the default workload (eager launches, 6 steps)
 #   2. the PMC passes (FETCH_SIZE | WRITE_SIZE | MFMA-busy | LDS bank conflicts; never combined with each other or with other trace
 #      domains), aggregated per kernel, then profiles/<tag>_pmc_traffic.json / _pmc_mfma.json (what bench.py reads for roofline.traffic / mfma_util)
-#   3. the default bench line (with its roofline and CPU legs) and one-flag variants of it; package power / clocks while it runs
+#   3. the --full bench line (the headline with its dedupe, roofline and CPU legs) and one-flag variants of it; package power / clocks while it runs
 tag=$1
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
@@ -25,7 +25,7 @@ cp $O/${tag}_pmc_traffic.json $O/${tag}_pmc_mfma.json profiles/   # the bench li
 # the default line; rocm-smi sampled beside it (package power and clocks during the timed steps)
 ( for i in $(seq 1 60); do /opt/rocm/bin/rocm-smi --showpower --showclocks --json 2>/dev/null | head -c 700; echo; sleep 1; done ) > $O/${tag}_bench_cfg3x16_power_samples.log 2>&1 &
 SMI=$!
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/${tag}_bench_cfg3x16.json 2> $O/${tag}_bench_cfg3x16.err
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/${tag}_bench_cfg3x16.json 2> $O/${tag}_bench_cfg3x16.err
 kill $SMI 2>/dev/null
 V="--steps 10 --warmup 3 --cpu-frames 0 --roofline-steps 0 --dedupe-steps 0"
 timeout 600 python bench.py $V > $O/${tag}_bench_variant_default.json 2>/dev/null
