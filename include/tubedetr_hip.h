@@ -344,7 +344,10 @@ int td_rows_segment_sum(const void* in, const int* idx, const int* ptr, void* ou
  * kernels in both dtypes); k,v [B][Lk] likewise; key_pad [B][Lk] uint8 (1 = ignore) or NULL.
  * scores = scale * q.k; probs [B][H][Lq][Lk] fp32 = softmax (pre-dropout, saved for backward);
  * out [B][Lq] rows of stride ldo = dropout(probs) @ v; wavg [B][Lq][Lk] fp32 = head average of the
- * post-dropout probabilities (what nn.MultiheadAttention returns) or NULL. */
+ * post-dropout probabilities (what nn.MultiheadAttention returns) or NULL.  hd = 32: any Lq, Lk >= 1 in both dtypes (Lk <= 512
+ * and, for the backward, Lq <= 640 on LDS-resident kernels; beyond, or at 2^32 elements and more, kernels that walk chunks of keys
+ * / queries with a 64-bit probability and dropout index - the same mask below 2^32).  hd = 64: Lk <= 512 and B*H*Lq*Lk < 2^32,
+ * else TD_ERR_INVALID.  bf16 callers that need no weights: td_mha_lean_fwd / _bwd below store nothing of size Lq x Lk. */
 int td_mha_fwd(const void* q, const void* k, const void* v, const uint8_t* key_pad, void* out, float* probs,
                float* wavg, int B, int H, int Lq, int Lk, int hd, int ldq, int ldk, int ldv, int ldo, float scale,
                float dropout_p, uint32_t dropout_seed, const uint32_t* dropout_counter, int dtype, td_stream_t stream);
@@ -400,8 +403,11 @@ int td_head_blocks_extract(const float* G, float alpha, float* dW, float* db, in
  * models/transformer.py:638-640: `weights` is dead there, SURVEY.md 8a'): nothing of size Lq x Lk is stored.  The forward
  * writes two softmax statistics per (batch, head, query) into `stats` (td_mha_lean_stats_bytes(B, H, Lq) bytes: 4 floats per
  * row); the backward recomputes the probabilities from q, k, key_pad and those statistics, takes sum_k P dP from dout . out
- * (`out` = the forward's output), and uses the third float of each row as scratch.  bf16, hd = 32, Lk <= 256, Lq <= 448,
- * 16-byte aligned rows; anything else returns TD_ERR_INVALID (use td_mha_fwd / td_mha_bwd).  Same dropout mask as td_mha_fwd. */
+ * (`out` = the forward's output), and uses the third float of each row as scratch.  bf16, hd = 32, 16-byte aligned rows, any
+ * Lq >= 1 and Lk >= 1 (Lk <= 256 with Lq <= 448: one key block per row; beyond: streaming kernels that walk key blocks with an
+ * online softmax, and query blocks for dK / dV; no float atomics, bit-reproducible); anything else returns TD_ERR_INVALID (use
+ * td_mha_fwd / td_mha_bwd).  Same dropout mask as td_mha_fwd; the dropout element index (b*H + h)*Lq*Lk + q*Lk + k is 64-bit,
+ * so B*H*Lq*Lk may exceed 2^32 (below 2^32 the mask is the 32-bit one). */
 size_t td_mha_lean_stats_bytes(int B, int H, int Lq);
 int td_mha_lean_fwd(const void* q, const void* k, const void* v, const uint8_t* key_pad, void* out, float* stats, int B, int H,
                     int Lq, int Lk, int hd, int ldq, int ldk, int ldv, int ldo, float scale, float dropout_p,

@@ -94,5 +94,11 @@ __device__ __forceinline__ uint32_t hash32(uint32_t seed, uint32_t idx) {
   return mix32(idx * 0x9E3779B1u + seed);
 }
 __device__ __forceinline__ bool dropout_keep(uint32_t seed, uint32_t idx, uint32_t thresh) { return hash32(seed, idx) >= thresh; }
+// 64-bit element index (tensors of 2^32 elements or more): the high word re-keys the seed, so every index below 2^32 draws
+// exactly dropout_keep(seed, (uint32_t)idx, thresh), and indices 2^32 apart draw independent masks.
+__device__ __forceinline__ bool dropout_keep64(uint32_t seed, uint64_t idx, uint32_t thresh) {
+  const uint32_t hi = (uint32_t)(idx >> 32);
+  return dropout_keep(hi ? mix32(seed ^ mix32(hi * 0x85EBCA77u)) : seed, (uint32_t)idx, thresh);
+}
 
 }  // namespace td

@@ -500,11 +500,11 @@ def mha_fwd(q: Tensor, k: Tensor, v: Tensor, key_pad: Optional[Tensor], H: int, 
 
 
 def mha_lean_ok(q: Tensor, k: Tensor, v: Tensor, H: int) -> bool:
-    """Can td_mha_lean_* take these projected rows?  (bf16, head dim 32, Lk <= 256, Lq <= 448, 16-byte aligned rows)"""
+    """Can td_mha_lean_* take these projected rows?  (bf16, head dim 32, 16-byte aligned rows; any Lq and Lk)"""
     if os.environ.get("TD_MHA_LEAN", "1") == "0":
         return False
     E = q.shape[2]
-    return (q.dtype == torch.bfloat16 and E // H == 32 and k.shape[1] <= 256 and q.shape[1] <= 448
+    return (q.dtype == torch.bfloat16 and E // H == 32
             and all(t_.stride(1) % 8 == 0 and t_.data_ptr() % 16 == 0 for t_ in (q, k, v)))
 
 
