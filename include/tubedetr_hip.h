@@ -473,6 +473,42 @@ int td_criterion_bwd(const float* dlosses, const float* g_l1, const float* g_gio
  * steds [n_videos][T][2] fp32 logits (-inf on padded positions), start_end [n_videos][2] int64. */
 int td_sted_decode(const float* steds, long long* start_end, int n_videos, int T, td_stream_t stream);
 
+/* ---- Device-side clip augmentation -------------------------------------------------------------------------------
+ * Resamples the decoded frames of many clips in ONE launch: the pixel work of the datasets' spatial transforms (random
+ * horizontal flip, resize, size crop, second resize: datasets/video_transforms.py:70-118,135-232,235-324, applied
+ * frame by frame on the host by cv2.resize in datasets/torch_videovision.py:125-161) and of the padding collate
+ * (NestedTensor.from_tensor_list, util/misc.py:158-170).  Per job:
+ *   src: uint8 rgb24, T frames of sh x sw pixels, 3 interleaved channels, `src_pitch` bytes per row and
+ *        `src_frame_stride` bytes per frame; flip = 1 reads source column j as column sw - 1 - j;
+ *   a virtual bilinear resize of the (flipped) source to rh x rw, of which the window (wy, wx, wh, ww) is produced;
+ *   planar = 0: dst = interleaved uint8 [T][wh][ww][3] (the intermediate between the two resizes of the training
+ *        transform, which rounds to uint8 in between);
+ *   planar = 1: dst = the batch's padded uint8 video [n][3][H][W]; frame t goes to [frame_off + t]: pixels inside
+ *        wh x ww are written, the rest of H x W is zero-filled, and mask [n][H][W] (bool bytes) gets 0 inside, 1 outside.
+ * Sampling rule (cv2.INTER_LINEAR / F.interpolate(mode="bilinear", align_corners=False), no antialiasing): output pixel
+ * (y, x) of the virtual image samples at cy = (y + 0.5) * sh / rh - 0.5 (cx alike), clamped to the source; coordinates
+ * are exact integers ((2y + 1) sh - rh over 2 rh: quotient = row, remainder = weight); value = floor(blend + 0.5).
+ * rh x rw = sh x sw is an exact copy.  `jobs` is a host array consumed before the call returns; the job table lives in
+ * caller-provided memory like td_conv_wgrad_batch's (table_host page-locked, table_dev device memory, both of
+ * td_clip_resample_table_bytes(n_jobs) bytes and untouched until the stream has passed the call).  No allocation, no
+ * synchronisation inside.  Sizes up to 16384 per side; a source row of more than 8192 pixels is rejected. */
+typedef struct td_resample_job {
+  const void* src;
+  long long src_frame_stride;
+  int src_pitch;
+  int T, sh, sw;
+  int flip;
+  int rh, rw;
+  int wy, wx, wh, ww;
+  void* dst;
+  int planar;
+  int frame_off;
+  int H, W; /* planar = 1: the padded frame; planar = 0: ignored */
+  void* mask; /* planar = 1 only */
+} td_resample_job;
+size_t td_clip_resample_table_bytes(int n_jobs);
+int td_clip_resample(const td_resample_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ import os
 import torch
 
 TD_F32, TD_BF16 = 0, 1
-EXPECTED_ABI = 10  # td_abi_version() of the library these signatures were written against
+EXPECTED_ABI = 11  # td_abi_version() of the library these signatures were written against
 _LIB_PATH = os.environ.get("TD_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libtubedetr_hip.so")  # (TD_HIP_LIB: an A/B build of the same ABI, tools/build_variant.sh)
 _lib = None
 
@@ -48,6 +48,12 @@ class LinearExDesc(C.Structure):
 class OptimSegment(C.Structure):
     """td_optim_segment."""
     _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("group", C.c_int), ("active", C.c_int)]
+
+
+class ResampleJob(C.Structure):
+    """td_resample_job."""
+    _fields_ = [("src", C.c_void_p), ("src_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("src_pitch", "T", "sh", "sw", "flip", "rh", "rw", "wy", "wx", "wh", "ww")] + \
+               [("dst", C.c_void_p)] + [(n, C.c_int) for n in ("planar", "frame_off", "H", "W")] + [("mask", C.c_void_p)]
 
 
 class Epilogue(C.Structure):
@@ -120,11 +126,13 @@ _SIGS = {
     "td_head_blocks_extract": [_P, _F, _P, _P, _I, _I, _P],
     "td_mha_lean_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _U32, _P, _I, _P],
     "td_mha_lean_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _U32, _P, _I, _P],
+    "td_clip_resample": [C.POINTER(ResampleJob), _I, _P, _P, _SZ, _P],
 }
 _SIZE_SIGS = {
     "td_grad_norm_ws_bytes": [],
     "td_mha_lean_stats_bytes": [_I, _I, _I],
     "td_conv_wgrad_batch_table_bytes": [_I],
+    "td_clip_resample_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],

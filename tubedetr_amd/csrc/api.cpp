@@ -130,4 +130,4 @@ extern "C" int td_prof_dump(const char* path) {
 }
 
 extern "C" const char* td_last_error(void) { return td::g_err; }
-extern "C" int td_abi_version(void) { return 10; }  // 10: td_mha_lean_fwd / _bwd take any Lq, Lk (9: td_pw_chain2, td_set_deterministic / td_get_deterministic)
+extern "C" int td_abi_version(void) { return 11; }  // 11: td_clip_resample (10: td_mha_lean_fwd / _bwd take any Lq, Lk; 9: td_pw_chain2, td_set_deterministic / td_get_deterministic)

@@ -26,6 +26,8 @@ class ClipPipeline:
         self.depth = depth
         self._slots: list = [None] * depth  # (pinned video, pinned mask, event of the last H2D out of them)
         self._next = 0
+        self._raw_slots: list = [None] * depth  # stage_raw: (pinned decoded frames, pinned job tables, event of the last work that read them)
+        self._raw_next = 0
 
     def _staging(self, n_frames: int, H: int, W: int):
         i = self._next % self.depth
@@ -78,6 +80,100 @@ class ClipPipeline:
             # extent of every frame inside the padded H x W (None for a uniform batch): the reference pads the NORMALISED
             # frames with zeros (NestedTensor.from_tensor_list, util/misc.py:158-170), so padded pixels must be 0 after the
             # device-side normalisation, not (0 - mean) / std
+            vhw_dev = torch.tensor(valid_hw, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True) if ragged else None
+            ids_dev = input_ids.pin_memory().to(self.device, non_blocking=True)
+            att_dev = attention_mask.pin_memory().to(self.device, non_blocking=True)
+            box_dev = target_boxes.pin_memory().to(self.device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        slot[2] = ev
+        return {"event": ev, "video": vid_dev, "mask": msk_dev, "slow_index": idx_dev, "valid_hw": vhw_dev, "durations": durations, "input_ids": ids_dev,
+                "attention_mask": att_dev, "target_boxes": box_dev, "inter_idx": [list(x) for x in inter_idx], "n_slow": len(slow_idx), "slow_index_host": tuple(slow_idx)}
+
+    def _raw_staging(self, n_bytes: int, table_bytes: int):
+        i = self._raw_next % self.depth
+        self._raw_next += 1
+        slot = self._raw_slots[i]
+        if slot is None or slot[0].numel() < n_bytes or slot[1].numel() < table_bytes:
+            slot = [torch.empty(n_bytes, dtype=torch.uint8, pin_memory=True), torch.empty(max(table_bytes, 4096), dtype=torch.uint8, pin_memory=True), None]
+            self._raw_slots[i] = slot
+        if slot[2] is not None:
+            slot[2].synchronize()  # the copy and the launches that last read this staging pair have finished
+        return slot
+
+    def stage_raw(self, videos: Sequence, plans: Sequence, input_ids: torch.Tensor, attention_mask: torch.Tensor, inter_idx: List[List[int]]) -> dict:
+        """videos: one uint8 (T_i, h_i, w_i, 3) CPU array / tensor per video AS DECODED (rgb24 at the video's own size,
+        datasets/vidstg.py:109-115); plans: its ``ClipPlan`` (tubedetr_amd.augment: ``make_video_transforms(...).plan``).
+        Packs the decoded frames into page-locked memory, copies them ONCE on the copy stream and enqueues the resample
+        launches there (td_clip_resample: flip, resize, crop, second resize, padding and padding mask); the ticket is
+        what ``stage`` returns, so ``collect`` gives the same batch dict.  ``target_boxes`` are the annotated frames'
+        boxes of the plans.  Temporal cropping stays with the caller: slice the array (and the targets) before this."""
+        from . import _hip
+        from .augment import resample_job
+
+        vids = []
+        for v in videos:
+            v = torch.as_tensor(v)
+            assert v.dtype == torch.uint8 and v.dim() == 4 and v.shape[3] == 3 and not v.is_cuda, "videos are uint8 (T, h, w, 3) on the host"
+            vids.append(v.contiguous())
+        assert len(vids) == len(plans) == len(inter_idx)
+        durations = [int(v.shape[0]) for v in vids]
+        H, W = max(int(p.hw[0]) for p in plans), max(int(p.hw[1]) for p in plans)
+        n = sum(durations)
+        boxes = []
+        for p, v, inter in zip(plans, vids, inter_idx):
+            assert len(p.targets) == v.shape[0] and tuple(p.src_hw) == tuple(v.shape[1:3]), "the plan was drawn for another clip"
+            if inter and inter[0] >= 0:  # number of boxes = number of frames in the annotated moment (datasets/vidstg.py:140-147)
+                n_boxed = len([t for t in p.targets if len(t["boxes"])])
+                assert n_boxed == inter[-1] - inter[0] + 1, (n_boxed, inter)
+            boxes += [t["boxes"] for t in p.targets if len(t["boxes"])]
+        target_boxes = torch.cat(boxes) if boxes else torch.zeros(0, 4)
+        offs, total = [], 0
+        for v in vids:
+            offs.append(total)
+            total += (v.numel() + 15) // 16 * 16
+        lib = _hip.lib()
+        n_first = sum(1 for p in plans if len(p.stages) == 2)
+        tb = [int(lib.td_clip_resample_table_bytes(n_first)), int(lib.td_clip_resample_table_bytes(len(plans)))]
+        raw_pin, tab_pin, _ = slot = self._raw_staging(total, tb[0] + tb[1])
+        for v, o in zip(vids, offs):
+            raw_pin[o : o + v.numel()].copy_(v.view(-1))
+        ragged = any(tuple(p.hw) != (H, W) for p in plans)
+        valid_hw = []
+        for p, d in zip(plans, durations):
+            valid_hw += [[int(p.hw[0]), int(p.hw[1])]] * d
+        k = self.stride
+        slow_idx, base = [], 0
+        for d in durations:  # slow clip = every k-th frame of each video (datasets/vidstg.py:250-251)
+            slow_idx += [base + j for j in range(0, d, k)]
+            base += d
+        with torch.cuda.stream(self.copy_stream):
+            raw_dev = raw_pin[:total].to(self.device, non_blocking=True)
+            vid_dev = torch.empty((n, 3, H, W), dtype=torch.uint8, device=self.device)
+            msk_dev = torch.empty((n, H, W), dtype=torch.bool, device=self.device)
+            tab_dev = torch.empty(tb[0] + tb[1], dtype=torch.uint8, device=self.device)
+            # raw_dev, tab_dev and the intermediates are allocated AND consumed on the copy stream only: the caching allocator
+            # hands their memory to later work of that stream alone, so they may go out of scope once the launches are enqueued
+            first, final, keep, off = [], [], [], 0
+            for v, p, o, d in zip(vids, plans, offs, durations):
+                src, sh, sw, flip = raw_dev.data_ptr() + o, int(v.shape[1]), int(v.shape[2]), p.flip
+                if len(p.stages) == 2:  # resize + crop into an interleaved uint8 intermediate (the reference rounds to uint8 there)
+                    s = p.stages[0]
+                    mid = torch.empty((d, s.wh, s.ww, 3), dtype=torch.uint8, device=self.device)
+                    keep.append(mid)
+                    first.append(resample_job(src, d, sh, sw, flip, s, mid.data_ptr()))
+                    src, sh, sw, flip = mid.data_ptr(), s.wh, s.ww, False
+                s = p.stages[-1]
+                assert (s.wh, s.ww) == tuple(p.hw)
+                final.append(resample_job(src, d, sh, sw, flip, s, vid_dev.data_ptr(), planar=True, frame_off=off, H=H, W=W, mask=msk_dev.data_ptr()))
+                off += d
+            t_off = 0
+            for jobs, nb in ((first, tb[0]), (final, tb[1])):
+                if jobs:
+                    arr = (_hip.ResampleJob * len(jobs))(*jobs)
+                    _hip.check(lib.td_clip_resample(arr, len(jobs), tab_pin.data_ptr() + t_off, tab_dev.data_ptr() + t_off, nb, _hip.stream_ptr()), "td_clip_resample")
+                t_off += nb
+            idx_dev = torch.tensor(slow_idx, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
             vhw_dev = torch.tensor(valid_hw, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True) if ragged else None
             ids_dev = input_ids.pin_memory().to(self.device, non_blocking=True)
             att_dev = attention_mask.pin_memory().to(self.device, non_blocking=True)
