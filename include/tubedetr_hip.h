@@ -367,7 +367,12 @@ int td_mha_bwd(const void* q, const void* k, const void* v, const void* dout, co
  * and value projections of the memory rows, 93 % of the decoder's FLOPs in the reference formulation, do not exist; the two
  * remaining products with W_k / W_v are GEMMs over the F query rows against the block-structured weights below.
  * u [F][H*E] T, mem / pos [F*S][E] T (pos may be NULL), key_pad [F][S] uint8 or NULL, probs [F][H][S] fp32, wavg [F][S] fp32 or
- * NULL, zext [F][ldz] T with ldz >= H*E + H (a multiple of 8). */
+ * NULL, zext [F][ldz] T with ldz >= H*E + H (a multiple of 8).
+ * Any S >= 1 is taken by td_cross_q1_fwd / _bwd / _bwd_coef (F * H * S < 2^32: the dropout index).  Up to S = 320 a workgroup keeps the
+ * frame's scores (bf16, S <= 256, no fp32 d_mem: the frame's rows too, on the matrix pipe) in LDS; above it the streaming instances walk
+ * the frame twice in chunks of 128 rows - statistics first (forward: running max / sum per head; backward: delta), outputs second - with
+ * LDS use independent of S: the VALU family in fp32 and wherever an fp32 d_mem is written, the matrix-pipe family for the other bf16
+ * launches.  No atomics in either range: the same call returns the same bits. */
 int td_cross_q1_fwd(const void* u, const void* mem, const void* pos, const uint8_t* key_pad, float* probs, float* wavg, void* zext,
                     int F, int S, int H, int E, int ldz, float dropout_p, uint32_t dropout_seed, const uint32_t* dropout_counter,
                     int dtype, td_stream_t stream);

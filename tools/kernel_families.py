@@ -39,7 +39,7 @@ def family(name: str):
         return FAMILY_OF_PROF_ID[5 if m.group(1) == "true" else 6]
     if re.search(r"td::(stem_pool|bottleneck_first3|bottleneck_resident3)_kernel", name):
         return FAMILY_OF_PROF_ID[7]
-    if re.search(r"td::cross_q1_(fwd|bwd)(_mfma)?_kernel|td::cross_q1_dmem_kernel", name):
+    if re.search(r"td::cross_q1_(fwd|bwd)(_stream)?(_mfma)?_kernel|td::cross_q1_dmem_kernel", name):
         return FAMILY_OF_PROF_ID[8]
     if "td::conv_wgrad_wide_batch_kernel" in name or "td::conv_wgrad_batch_kernel" in name:
         return FAMILY_OF_PROF_ID[2]

@@ -19,7 +19,9 @@
 // The kernels are HBM-bound by the memory rows.  Two families: the templates right below do the arithmetic in fp32 on the VALU in
 // both dtypes (24 FLOP per loaded byte; the exact-fp32 parity mode, S > 256); in bf16 both products of a frame - and the gradient of
 // the shared memory over all layers - are v_mfma_f32_16x16x32_bf16 tiles (cross_q1_fwd_mfma_kernel, cross_q1_bwd_mfma_kernel,
-// cross_q1_dmem_kernel further down): the rows come from HBM once per layer and direction.
+// cross_q1_dmem_kernel further down): the rows come from HBM once per layer and direction.  These kernels keep a frame's scores (and
+// row image) in LDS and serve up to CQ_RESIDENT_MAX = 320 rows per frame; beyond it the streaming instances of both families (further
+// down) walk the frame twice in chunks: any S.
 //
 // Layout of a VALU workgroup (256 threads, one frame): lane l of every wavefront owns channels 4l .. 4l+3; wavefront w walks the
 // blocks of 8 (4) consecutive rows - their loads are issued back to back -; the 8 per-head partial dot products of a row are
@@ -646,6 +648,632 @@ __global__ __launch_bounds__(512) void cross_q1_bwd_mfma_kernel(CrossQ1Params p)
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Streaming instances: any S (the launchers use them above CQ_RESIDENT_MAX rows per frame).  The kernels above keep three arrays of
+// S x 8 values (scores, probabilities after dropout, ds) - and, on the matrix pipe, the frame's row image - in LDS; these walk the frame
+// in chunks of CQ_CHUNK rows, twice, and keep per head only what a pass hands to the next one - the S-sized arrays are recomputed:
+//   forward   pass 1: scores of the chunk -> running maximum and running sum of exponentials per head
+//             pass 2: the scores again -> pr = exp(score - max) / sum with the FINAL statistics, probs, dropout, wavg, z += pd x
+//   backward  pass 1: g = d_z . x_s + d(sum pd) + dwavg / 8, dp = keep ? g * scale : 0 -> delta_h = sum_s pr dp
+//             pass 2: dp again -> ds = pr (dp - delta), the coefficient rows / the fp32 d(memory) rows, d_u += ds (x + pos)
+// One workgroup per frame, no atomics, LDS use independent of S; every reduction has a fixed order (bit-reproducible run to run).
+// The dropout key is the resident kernels' (seed, (f * 8 + h) * S + s).  A head whose rows are all masked so far has a running maximum
+// of -inf: the update is skipped (never exp(-inf - (-inf))); masked rows get probability exactly 0.
+constexpr int CQ_CHUNK = 128;         // rows per chunk (two 78 KiB matrix-pipe workgroups share a CU's 160 KiB of LDS)
+constexpr int CQ_RESIDENT_MAX = 320;  // up to here the resident kernels above serve (their dispatch and results are unchanged)
+
+// running (max, sum) of one head over a chunk: v[] = this lane's scores of the chunk (-inf: masked / past the end)
+template <int NV>
+__device__ __forceinline__ void online_max_sum(const float (&v)[NV], float& mrun, float& lrun) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) mx = fmaxf(mx, v[i]);
+  mx = wave_max(mx);
+  const float mnew = fmaxf(mrun, mx);
+  if (mnew > -INFINITY) {  // wave-uniform; an all-masked prefix leaves (-inf, 0) untouched
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) sum += v[i] > -INFINITY ? __expf(v[i] - mnew) : 0.f;
+    sum = wave_sum(sum);
+    lrun = (mrun > -INFINITY ? lrun * __expf(mrun - mnew) : 0.f) + sum;
+    mrun = mnew;
+  }
+}
+
+__device__ __forceinline__ void store_coef_row(const CrossQ1Params& p, size_t grow, const float* sDS, const float* sPD, int s) {
+  const float4 a = *(const float4*)(sDS + s * QH), b = *(const float4*)(sDS + s * QH + 4);
+  const float4 c = *(const float4*)(sPD + s * QH), d = *(const float4*)(sPD + s * QH + 4);
+  uint4 lo, hi;
+  lo.x = (uint32_t)f32_to_bf16(a.x) | ((uint32_t)f32_to_bf16(a.y) << 16);
+  lo.y = (uint32_t)f32_to_bf16(a.z) | ((uint32_t)f32_to_bf16(a.w) << 16);
+  lo.z = (uint32_t)f32_to_bf16(b.x) | ((uint32_t)f32_to_bf16(b.y) << 16);
+  lo.w = (uint32_t)f32_to_bf16(b.z) | ((uint32_t)f32_to_bf16(b.w) << 16);
+  hi.x = (uint32_t)f32_to_bf16(c.x) | ((uint32_t)f32_to_bf16(c.y) << 16);
+  hi.y = (uint32_t)f32_to_bf16(c.z) | ((uint32_t)f32_to_bf16(c.w) << 16);
+  hi.z = (uint32_t)f32_to_bf16(d.x) | ((uint32_t)f32_to_bf16(d.y) << 16);
+  hi.w = (uint32_t)f32_to_bf16(d.z) | ((uint32_t)f32_to_bf16(d.w) << 16);
+  uint4* dst = (uint4*)(p.coef + grow * (size_t)p.coef_ld + p.coef_col);
+  dst[0] = lo;
+  dst[1] = hi;
+}
+
+// fp32 / VALU family (both dtypes; the exact-fp32 parity mode and every launch that writes an fp32 d(memory)): cross_q1_fwd_kernel's lane
+// layout per chunk.  Wavefront w normalises heads w and w + 4 in both passes: their running statistics never leave its registers.
+template <typename T>
+__global__ __launch_bounds__(256) void cross_q1_fwd_stream_kernel(CrossQ1Params p) {
+  constexpr int C = CQ_CHUNK, KB = 8, NV = C / 64;
+  __shared__ __attribute__((aligned(16))) float sS[2][QH * C];   // [h][s] scores of a chunk (pass 1 alternates the two)
+  __shared__ __attribute__((aligned(16))) float sP[C * QH];      // [s][h] probabilities after dropout
+  __shared__ __attribute__((aligned(16))) float sZ[4 * QH * QE];
+  __shared__ float sSp[QH];
+  const int S = p.S;
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int f = blockIdx.x;
+  const size_t row0 = (size_t)f * S;
+  float ur[QH][4];
+#pragma unroll
+  for (int h = 0; h < QH; ++h) {
+    const float4 v = load4<T>(p.u, (size_t)f * QH * QE + h * QE + 4 * lane);
+    ur[h][0] = v.x; ur[h][1] = v.y; ur[h][2] = v.z; ur[h][3] = v.w;
+  }
+  const int hl = head_of_lane(lane);
+  auto scores = [&](int c0, int n, float* dst) {
+    for (int s0 = wave * KB; s0 < n; s0 += 4 * KB) {
+      float4 m[KB];
+#pragma unroll
+      for (int j = 0; j < KB; ++j) m[j] = load4<T>(p.mem, (row0 + c0 + min(s0 + j, n - 1)) * QE + 4 * lane);
+      if (p.pos) {
+#pragma unroll
+        for (int j = 0; j < KB; ++j) {
+          const float4 q = load4<T>(p.pos, (row0 + c0 + min(s0 + j, n - 1)) * QE + 4 * lane);
+          m[j].x += q.x; m[j].y += q.y; m[j].z += q.z; m[j].w += q.w;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < KB; ++j) {
+        float part[QH];
+#pragma unroll
+        for (int h = 0; h < QH; ++h) part[h] = dot4(m[j], ur[h]);
+        const float tot = head_reduce8(part, lane);
+        if (lane < QH && s0 + j < n) dst[hl * C + s0 + j] = tot;
+      }
+    }
+  };
+  // this lane's scores of head h in the chunk, key padding applied
+  auto masked_scores = [&](const float* row, int c0, int n, float (&v)[NV]) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int s = lane + 64 * i;
+      v[i] = -INFINITY;
+      if (s < n && !(p.kpm && p.kpm[row0 + c0 + s])) v[i] = row[s];
+    }
+  };
+  float mrun[2] = {-INFINITY, -INFINITY}, lrun[2] = {0.f, 0.f};
+  {
+    int k = 0;
+    for (int c0 = 0; c0 < S; c0 += C, ++k) {
+      const int n = min(C, S - c0);
+      float* buf = sS[k & 1];
+      scores(c0, n, buf);
+      __syncthreads();  // (one barrier per chunk: the next chunk writes the other buffer)
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        float v[NV];
+        masked_scores(buf + (wave + 4 * hh) * C, c0, n, v);
+        online_max_sum<NV>(v, mrun[hh], lrun[hh]);
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t seed = effective_seed(p.seed, p.seed_dev);
+  const float inv[2] = {lrun[0] > 0.f ? 1.f / lrun[0] : 0.f, lrun[1] > 0.f ? 1.f / lrun[1] : 0.f};
+  float spd[2] = {0.f, 0.f};
+  float z[QH][4];
+#pragma unroll
+  for (int h = 0; h < QH; ++h) z[h][0] = z[h][1] = z[h][2] = z[h][3] = 0.f;
+  for (int c0 = 0; c0 < S; c0 += C) {
+    const int n = min(C, S - c0);
+    scores(c0, n, sS[0]);
+    __syncthreads();
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const int h = wave + 4 * hh;
+      float v[NV];
+      masked_scores(sS[0] + h * C, c0, n, v);
+      const size_t prow = ((size_t)f * QH + h) * S + c0;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int s = lane + 64 * i;
+        if (s < n) {
+          float pr = v[i] > -INFINITY ? __expf(v[i] - mrun[hh]) * inv[hh] : 0.f;
+          p.probs[prow + s] = pr;
+          if (p.drop_thresh) pr = dropout_keep(seed, (uint32_t)(prow + s), p.drop_thresh) ? pr * p.drop_scale : 0.f;
+          sP[s * QH + h] = pr;
+          spd[hh] += pr;
+        }
+      }
+    }
+    __syncthreads();
+    if (p.wavg)
+      for (int s = t; s < n; s += 256) {
+        const float4 a = *(const float4*)(sP + s * QH), b = *(const float4*)(sP + s * QH + 4);
+        p.wavg[row0 + c0 + s] = (a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w) * (1.f / QH);
+      }
+    for (int s0 = wave * KB; s0 < n; s0 += 4 * KB) {
+      float4 m[KB];
+#pragma unroll
+      for (int j = 0; j < KB; ++j) m[j] = load4<T>(p.mem, (row0 + c0 + min(s0 + j, n - 1)) * QE + 4 * lane);
+#pragma unroll
+      for (int j = 0; j < KB; ++j) {
+        if (s0 + j >= n) break;  // wave-uniform
+        const float4 a = *(const float4*)(sP + (s0 + j) * QH), b = *(const float4*)(sP + (s0 + j) * QH + 4);
+        const float pd[QH] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int h = 0; h < QH; ++h) {
+          z[h][0] += pd[h] * m[j].x; z[h][1] += pd[h] * m[j].y; z[h][2] += pd[h] * m[j].z; z[h][3] += pd[h] * m[j].w;
+        }
+      }
+    }
+    // (the next chunk's scores go to sS, which nobody reads any more; its sP writes follow its first barrier)
+  }
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) {
+    const float tot = wave_sum(spd[hh]);
+    if (lane == 0) sSp[wave + 4 * hh] = tot;
+  }
+#pragma unroll
+  for (int h = 0; h < QH; ++h) *(float4*)(sZ + wave * QH * QE + h * QE + 4 * lane) = make_float4(z[h][0], z[h][1], z[h][2], z[h][3]);
+  __syncthreads();
+  reduce_store_rows<T>(sZ, p.zext, (size_t)f * p.ldz, t);
+  if (t < QH) Elem<T>::store(p.zext, (size_t)f * p.ldz + QH * QE + t, sSp[t]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cross_q1_bwd_stream_kernel(CrossQ1Params p) {
+  constexpr int C = CQ_CHUNK, KB = 8, KB2 = 4, NV = C / 64;
+  __shared__ __attribute__((aligned(16))) float sS[2][QH * C];  // [h][s] d_z . x_s of a chunk (pass 1 alternates the two)
+  __shared__ __attribute__((aligned(16))) float sDS[C * QH];    // [s][h]
+  __shared__ __attribute__((aligned(16))) float sPD[C * QH];    // [s][h]
+  __shared__ __attribute__((aligned(16))) float sU[4 * QH * QE];
+  const int S = p.S;
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int f = blockIdx.x;
+  const size_t row0 = (size_t)f * S;
+  float ur[QH][4], dzr[QH][4];
+#pragma unroll
+  for (int h = 0; h < QH; ++h) {
+    const float4 v = load4<T>(p.u, (size_t)f * QH * QE + h * QE + 4 * lane);
+    ur[h][0] = v.x; ur[h][1] = v.y; ur[h][2] = v.z; ur[h][3] = v.w;
+    const float4 g = load4<T>(p.dz, (size_t)f * p.ldz + h * QE + 4 * lane);
+    dzr[h][0] = g.x; dzr[h][1] = g.y; dzr[h][2] = g.z; dzr[h][3] = g.w;
+  }
+  const int hl = head_of_lane(lane);
+  auto gdot = [&](int c0, int n, float* dst) {
+    for (int s0 = wave * KB; s0 < n; s0 += 4 * KB) {
+      float4 m[KB];
+#pragma unroll
+      for (int j = 0; j < KB; ++j) m[j] = load4<T>(p.mem, (row0 + c0 + min(s0 + j, n - 1)) * QE + 4 * lane);
+#pragma unroll
+      for (int j = 0; j < KB; ++j) {
+        float part[QH];
+#pragma unroll
+        for (int h = 0; h < QH; ++h) part[h] = dot4(m[j], dzr[h]);
+        const float tot = head_reduce8(part, lane);
+        if (lane < QH && s0 + j < n) dst[hl * C + s0 + j] = tot;
+      }
+    }
+  };
+  const uint32_t seed = effective_seed(p.seed, p.seed_dev);
+  float dsp[2];
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) dsp[hh] = Elem<T>::load(p.dz, (size_t)f * p.ldz + QH * QE + wave + 4 * hh);
+  // row s (< n) of the chunk, head h: the probability, the dropout decision and dP
+  auto row_dp = [&](const float* row, int hh, size_t prow, int c0, int s, float& pr, bool& keep) {
+    pr = p.probs[prow + s];
+    keep = !p.drop_thresh || dropout_keep(seed, (uint32_t)(prow + s), p.drop_thresh);
+    float g = row[s] + dsp[hh];
+    if (p.dwavg) g += p.dwavg[row0 + c0 + s] * (1.f / QH);
+    return keep ? g * p.drop_scale : 0.f;
+  };
+  float delta[2] = {0.f, 0.f};
+  {
+    int k = 0;
+    for (int c0 = 0; c0 < S; c0 += C, ++k) {
+      const int n = min(C, S - c0);
+      float* buf = sS[k & 1];
+      gdot(c0, n, buf);
+      __syncthreads();
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        const int h = wave + 4 * hh;
+        const size_t prow = ((size_t)f * QH + h) * S + c0;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+          const int s = lane + 64 * i;
+          if (s < n) {
+            float pr;
+            bool keep;
+            const float dp = row_dp(buf + h * C, hh, prow, c0, s, pr, keep);
+            delta[hh] += pr * dp;
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int hh = 0; hh < 2; ++hh) delta[hh] = wave_sum(delta[hh]);
+  __syncthreads();
+  float du[QH][4];
+#pragma unroll
+  for (int h = 0; h < QH; ++h) du[h][0] = du[h][1] = du[h][2] = du[h][3] = 0.f;
+  for (int c0 = 0; c0 < S; c0 += C) {
+    const int n = min(C, S - c0);
+    gdot(c0, n, sS[0]);
+    __syncthreads();
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const int h = wave + 4 * hh;
+      const size_t prow = ((size_t)f * QH + h) * S + c0;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int s = lane + 64 * i;
+        if (s < n) {
+          float pr;
+          bool keep;
+          const float dp = row_dp(sS[0] + h * C, hh, prow, c0, s, pr, keep);
+          sDS[s * QH + h] = pr * (dp - delta[hh]);
+          sPD[s * QH + h] = keep ? pr * p.drop_scale : 0.f;
+        }
+      }
+    }
+    __syncthreads();
+    if (p.coef)
+      for (int s = t; s < n; s += 256) store_coef_row(p, row0 + c0 + s, sDS, sPD, s);
+    for (int s0 = wave * KB2; s0 < n; s0 += 4 * KB2) {
+      float4 m[KB2], o[KB2];
+#pragma unroll
+      for (int j = 0; j < KB2; ++j) m[j] = load4<T>(p.mem, (row0 + c0 + min(s0 + j, n - 1)) * QE + 4 * lane);
+      if (p.pos) {
+#pragma unroll
+        for (int j = 0; j < KB2; ++j) {
+          const float4 q = load4<T>(p.pos, (row0 + c0 + min(s0 + j, n - 1)) * QE + 4 * lane);
+          m[j].x += q.x; m[j].y += q.y; m[j].z += q.z; m[j].w += q.w;
+        }
+      }
+      if (p.accumulate) {
+#pragma unroll
+        for (int j = 0; j < KB2; ++j) o[j] = *(const float4*)(p.dmem + (row0 + c0 + min(s0 + j, n - 1)) * QE + 4 * lane);
+      }
+#pragma unroll
+      for (int j = 0; j < KB2; ++j) {
+        if (s0 + j >= n) break;  // wave-uniform
+        const int s = s0 + j;
+        const float4 a = *(const float4*)(sDS + s * QH), b = *(const float4*)(sDS + s * QH + 4);
+        const float4 c = *(const float4*)(sPD + s * QH), d = *(const float4*)(sPD + s * QH + 4);
+        const float ds[QH] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        const float pd[QH] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
+        float4 g = p.accumulate ? o[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int h = 0; h < QH; ++h) {
+          du[h][0] += ds[h] * m[j].x; du[h][1] += ds[h] * m[j].y; du[h][2] += ds[h] * m[j].z; du[h][3] += ds[h] * m[j].w;
+        }
+        if (!p.dmem) continue;
+#pragma unroll
+        for (int h = 0; h < QH; ++h) {
+          g.x += ds[h] * ur[h][0] + pd[h] * dzr[h][0];
+          g.y += ds[h] * ur[h][1] + pd[h] * dzr[h][1];
+          g.z += ds[h] * ur[h][2] + pd[h] * dzr[h][2];
+          g.w += ds[h] * ur[h][3] + pd[h] * dzr[h][3];
+        }
+        *(float4*)(p.dmem + (row0 + c0 + s) * QE + 4 * lane) = g;
+      }
+    }
+    // (sS is free for the next chunk; its sDS / sPD writes follow its first barrier)
+  }
+#pragma unroll
+  for (int h = 0; h < QH; ++h) *(float4*)(sU + wave * QH * QE + h * QE + 4 * lane) = make_float4(du[h][0], du[h][1], du[h][2], du[h][3]);
+  __syncthreads();
+  reduce_store_rows<T>(sU, p.du, (size_t)f * QH * QE, t);
+}
+
+// bf16 / matrix-pipe family: the two products of cross_q1_fwd_mfma_kernel / cross_q1_bwd_mfma_kernel per chunk.  Eight wavefronts, one
+// 16-row tile each per chunk; wavefront w normalises head w in both passes.  Pass 1 needs no row image; in pass 2 the image holds the
+// chunk (64 KiB), rebuilt per chunk - rows past the end of the frame are zeros, and so are their probabilities.
+__global__ __launch_bounds__(512) void cross_q1_fwd_stream_mfma_kernel(CrossQ1Params p) {
+  constexpr int C = CQ_CHUNK, HALF = C * 256, NV = C / 64;
+  __shared__ __attribute__((aligned(16))) char sX[2 * HALF];
+  __shared__ __attribute__((aligned(16))) float sS[2][QH * C];  // [h][s] scores of a chunk (pass 1 alternates the two)
+  __shared__ __attribute__((aligned(16))) float sP[C * QH];     // [s][h] probabilities after dropout (wavg)
+  __shared__ __attribute__((aligned(16))) u16 sPb[QH * C];      // the same in bf16, [h][s]: A operand of the sums
+  __shared__ float sSp[QH];
+  const int S = p.S;
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int lr = lane & 15, lg = lane >> 4, jrow = lr >> 2, q = lr & 3;
+  const int f = blockIdx.x;
+  const size_t row0 = (size_t)f * S;
+  const u16* mem = (const u16*)p.mem;
+  const u16* pos = (const u16*)p.pos;
+  uint4 ua[8];
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    ua[ks] = make_uint4(0u, 0u, 0u, 0u);
+    if (lr < QH) ua[ks] = *(const uint4*)((const u16*)p.u + ((size_t)f * QH + lr) * QE + ks * 32 + lg * 8);
+  }
+  const int row = wave * 16 + lr;  // this lane's row of every chunk
+  // scores of the wavefront's tile of chunk c0 -> dst [h][s]; with_image: the rows into the image too
+  auto tile = [&](int c0, float* dst, bool with_image) {
+    const bool valid = c0 + row < S;
+    uint4 xm[8], xp[8];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      xm[ks] = make_uint4(0u, 0u, 0u, 0u);
+      if (valid) xm[ks] = *(const uint4*)(mem + (row0 + c0 + row) * QE + ks * 32 + lg * 8);
+    }
+    if (pos) {
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        xp[ks] = make_uint4(0u, 0u, 0u, 0u);
+        if (valid) xp[ks] = *(const uint4*)(pos + (row0 + c0 + row) * QE + ks * 32 + lg * 8);
+      }
+    }
+    cq_f4 acc = cq_f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const cq_bf8*)&ua[ks], *(const cq_bf8*)&xm[ks], acc, 0, 0, 0);
+    if (pos) {
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const cq_bf8*)&ua[ks], *(const cq_bf8*)&xp[ks], acc, 0, 0, 0);
+    }
+    if (lg < 2 && valid) {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) dst[(4 * lg + rr) * C + row] = acc[rr];
+    }
+    if (with_image) {
+      const int swz = (row & 3) | (((row >> 3) & 1) << 2);
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        const int c = 4 * ks + lg, hf = c >> 4, c16 = c & 15;
+        const int slot = (((c16 >> 1) ^ swz) << 1) | (c16 & 1);
+        *(uint4*)(sX + hf * HALF + row * 256 + slot * 16) = xm[ks];
+      }
+    }
+  };
+  const int h = wave;  // one head per wavefront
+  auto masked_scores = [&](const float* srow, int c0, int n, float (&v)[NV]) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int s = lane + 64 * i;
+      v[i] = -INFINITY;
+      if (s < n && !(p.kpm && p.kpm[row0 + c0 + s])) v[i] = srow[s];
+    }
+  };
+  float mrun = -INFINITY, lrun = 0.f;
+  {
+    int k = 0;
+    for (int c0 = 0; c0 < S; c0 += C, ++k) {
+      const int n = min(C, S - c0);
+      float* buf = sS[k & 1];
+      tile(c0, buf, false);
+      __syncthreads();
+      float v[NV];
+      masked_scores(buf + h * C, c0, n, v);
+      online_max_sum<NV>(v, mrun, lrun);
+    }
+  }
+  __syncthreads();
+  const uint32_t seed = effective_seed(p.seed, p.seed_dev);
+  const float inv = lrun > 0.f ? 1.f / lrun : 0.f;
+  float spd = 0.f;
+  cq_f4 z[2];
+#pragma unroll
+  for (int n2 = 0; n2 < 2; ++n2) z[n2] = cq_f4{0.f, 0.f, 0.f, 0.f};
+  const int fsw = jrow | ((lg & 1) << 2);
+  const char* half = sX + (wave >> 2) * HALF;
+  for (int c0 = 0; c0 < S; c0 += C) {
+    const int n = min(C, S - c0);
+    tile(c0, sS[0], true);
+    __syncthreads();
+    {
+      float v[NV];
+      masked_scores(sS[0] + h * C, c0, n, v);
+      const size_t prow = ((size_t)f * QH + h) * S + c0;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int s = lane + 64 * i;
+        float pr = 0.f;
+        if (s < n) {
+          pr = v[i] > -INFINITY ? __expf(v[i] - mrun) * inv : 0.f;
+          p.probs[prow + s] = pr;
+          if (p.drop_thresh) pr = dropout_keep(seed, (uint32_t)(prow + s), p.drop_thresh) ? pr * p.drop_scale : 0.f;
+          sP[s * QH + h] = pr;
+          spd += pr;
+        }
+        sPb[h * C + s] = f32_to_bf16(pr);
+      }
+    }
+    __syncthreads();
+    if (p.wavg && t < n) {
+      const float4 a = *(const float4*)(sP + t * QH), b = *(const float4*)(sP + t * QH + 4);
+      p.wavg[row0 + c0 + t] = (a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w) * (1.f / QH);
+    }
+    for (int ks = 0; ks < (n + 31) / 32; ++ks) {
+      uint4 pa = make_uint4(0u, 0u, 0u, 0u);
+      if (lr < QH) pa = *(const uint4*)(sPb + lr * C + ks * 32 + lg * 8);
+      const int r0 = ks * 32 + 8 * lg + jrow;
+#pragma unroll
+      for (int n2 = 0; n2 < 2; ++n2) {
+        const int blk16 = (wave & 3) * 2 + n2;
+        const int cb = ((blk16 ^ fsw) << 5) + q * 8;
+        const cq_bf4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) cq_bf4*)(half + r0 * 256 + cb));
+        const cq_bf4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) cq_bf4*)(half + (r0 + 4) * 256 + cb));
+        const cq_bf8 b = cq_bf8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        z[n2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const cq_bf8*)&pa, b, z[n2], 0, 0, 0);
+      }
+    }
+    __syncthreads();  // the image, sP and sPb are rebuilt by the next chunk
+  }
+  spd = wave_sum(spd);
+  if (lane == 0) sSp[h] = spd;
+  if (lg < 2) {
+    u16* zrow = (u16*)p.zext + (size_t)f * p.ldz;
+#pragma unroll
+    for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) zrow[(4 * lg + rr) * QE + wave * 32 + 16 * n2 + lr] = f32_to_bf16(z[n2][rr]);
+  }
+  __syncthreads();
+  if (t < QH) ((u16*)p.zext)[(size_t)f * p.ldz + QH * QE + t] = f32_to_bf16(sSp[t]);
+}
+
+// (the memory gradient deferred or not wanted, as for cross_q1_bwd_mfma_kernel.)  Pass 1 multiplies d_z with the memory rows alone; pass 2
+// fetches the positional rows too and builds the image of their sum for d_u.
+__global__ __launch_bounds__(512) void cross_q1_bwd_stream_mfma_kernel(CrossQ1Params p) {
+  constexpr int C = CQ_CHUNK, HALF = C * 256, NV = C / 64;
+  __shared__ __attribute__((aligned(16))) char sX[2 * HALF];
+  __shared__ __attribute__((aligned(16))) float sS[QH * C];     // [h][s] d_z . x_s of a chunk
+  __shared__ __attribute__((aligned(16))) float sDS[C * QH];    // [s][h]
+  __shared__ __attribute__((aligned(16))) float sPD[C * QH];    // [s][h]
+  __shared__ __attribute__((aligned(16))) u16 sDSb[QH * C];     // ds in bf16, [h][s]: A operand of d_u
+  const int S = p.S;
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int lr = lane & 15, lg = lane >> 4, jrow = lr >> 2, q = lr & 3;
+  const int f = blockIdx.x;
+  const size_t row0 = (size_t)f * S;
+  const u16* mem = (const u16*)p.mem;
+  const u16* pos = (const u16*)p.pos;
+  uint4 da[8];
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    da[ks] = make_uint4(0u, 0u, 0u, 0u);
+    if (lr < QH) da[ks] = *(const uint4*)((const u16*)p.dz + (size_t)f * p.ldz + lr * QE + ks * 32 + lg * 8);
+  }
+  const int row = wave * 16 + lr;
+  auto tile = [&](int c0, bool with_image) {
+    const bool valid = c0 + row < S;
+    uint4 xm[8], xp[8];
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      xm[ks] = make_uint4(0u, 0u, 0u, 0u);
+      if (valid) xm[ks] = *(const uint4*)(mem + (row0 + c0 + row) * QE + ks * 32 + lg * 8);
+    }
+    if (with_image && pos) {
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        xp[ks] = make_uint4(0u, 0u, 0u, 0u);
+        if (valid) xp[ks] = *(const uint4*)(pos + (row0 + c0 + row) * QE + ks * 32 + lg * 8);
+      }
+    }
+    cq_f4 acc = cq_f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const cq_bf8*)&da[ks], *(const cq_bf8*)&xm[ks], acc, 0, 0, 0);
+    if (lg < 2 && valid) {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) sS[(4 * lg + rr) * C + row] = acc[rr];
+    }
+    if (with_image) {
+      const int swz = (row & 3) | (((row >> 3) & 1) << 2);
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        uint4 v = xm[ks];
+        if (pos) {
+          const uint32_t a_[4] = {xm[ks].x, xm[ks].y, xm[ks].z, xm[ks].w}, b_[4] = {xp[ks].x, xp[ks].y, xp[ks].z, xp[ks].w};
+          uint32_t o_[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float lo = __uint_as_float(a_[e] << 16) + __uint_as_float(b_[e] << 16);
+            const float hi = __uint_as_float(a_[e] & 0xFFFF0000u) + __uint_as_float(b_[e] & 0xFFFF0000u);
+            o_[e] = (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
+          }
+          v = make_uint4(o_[0], o_[1], o_[2], o_[3]);
+        }
+        const int c = 4 * ks + lg, hf = c >> 4, c16 = c & 15;
+        const int slot = (((c16 >> 1) ^ swz) << 1) | (c16 & 1);
+        *(uint4*)(sX + hf * HALF + row * 256 + slot * 16) = v;
+      }
+    }
+  };
+  const uint32_t seed = effective_seed(p.seed, p.seed_dev);
+  const int h = wave;  // one head per wavefront
+  const float dsp = Elem<u16>::load(p.dz, (size_t)f * p.ldz + QH * QE + h);
+  const float* srow = sS + h * C;
+  auto row_dp = [&](size_t prow, int c0, int s, float& pr, bool& keep) {
+    pr = p.probs[prow + s];
+    keep = !p.drop_thresh || dropout_keep(seed, (uint32_t)(prow + s), p.drop_thresh);
+    float g = srow[s] + dsp;
+    if (p.dwavg) g += p.dwavg[row0 + c0 + s] * (1.f / QH);
+    return keep ? g * p.drop_scale : 0.f;
+  };
+  float delta = 0.f;
+  for (int c0 = 0; c0 < S; c0 += C) {
+    const int n = min(C, S - c0);
+    tile(c0, false);
+    __syncthreads();
+    const size_t prow = ((size_t)f * QH + h) * S + c0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int s = lane + 64 * i;
+      if (s < n) {
+        float pr;
+        bool keep;
+        const float dp = row_dp(prow, c0, s, pr, keep);
+        delta += pr * dp;
+      }
+    }
+    __syncthreads();
+  }
+  delta = wave_sum(delta);
+  cq_f4 z[2];
+#pragma unroll
+  for (int n2 = 0; n2 < 2; ++n2) z[n2] = cq_f4{0.f, 0.f, 0.f, 0.f};
+  const int fsw = jrow | ((lg & 1) << 2);
+  const char* half = sX + (wave >> 2) * HALF;
+  for (int c0 = 0; c0 < S; c0 += C) {
+    const int n = min(C, S - c0);
+    tile(c0, true);
+    __syncthreads();
+    {
+      const size_t prow = ((size_t)f * QH + h) * S + c0;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int s = lane + 64 * i;
+        float ds = 0.f;
+        if (s < n) {
+          float pr;
+          bool keep;
+          const float dp = row_dp(prow, c0, s, pr, keep);
+          ds = pr * (dp - delta);
+          sDS[s * QH + h] = ds;
+          sPD[s * QH + h] = keep ? pr * p.drop_scale : 0.f;
+        }
+        sDSb[h * C + s] = f32_to_bf16(ds);
+      }
+    }
+    __syncthreads();
+    if (p.coef && t < n) store_coef_row(p, row0 + c0 + t, sDS, sPD, t);
+    for (int ks = 0; ks < (n + 31) / 32; ++ks) {
+      uint4 pa = make_uint4(0u, 0u, 0u, 0u);
+      if (lr < QH) pa = *(const uint4*)(sDSb + lr * C + ks * 32 + lg * 8);
+      const int r0 = ks * 32 + 8 * lg + jrow;
+#pragma unroll
+      for (int n2 = 0; n2 < 2; ++n2) {
+        const int blk16 = (wave & 3) * 2 + n2;
+        const int cb = ((blk16 ^ fsw) << 5) + q * 8;
+        const cq_bf4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) cq_bf4*)(half + r0 * 256 + cb));
+        const cq_bf4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) cq_bf4*)(half + (r0 + 4) * 256 + cb));
+        const cq_bf8 b = cq_bf8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        z[n2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const cq_bf8*)&pa, b, z[n2], 0, 0, 0);
+      }
+    }
+    __syncthreads();  // the image, sS, sDS, sPD and sDSb are rebuilt by the next chunk
+  }
+  if (lg < 2) {
+    u16* drow = (u16*)p.du + (size_t)f * QH * QE;
+#pragma unroll
+    for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) drow[(4 * lg + rr) * QE + wave * 32 + 16 * n2 + lr] = f32_to_bf16(z[n2][rr]);
+  }
+}
+
 // d(memory) of all the layers at once (bf16 mode): per frame  D [S][E] = C [S][KP] . B [KP][E]  with C the coefficient rows the
 // layers' backward kernels left (k = 16 * layer + {ds[h], 8 + pd[h]}) and B row k = u_layer[h] or d_z_layer[h] - 10 x 16 output
 // tiles of v_mfma_f32_16x16x32_bf16 over KP / 32 k-steps.  C fragments are 16 contiguous bytes of a row (k along the lane's eight
@@ -855,8 +1483,7 @@ extern "C" int td_cross_q1_fwd(const void* u, const void* mem, const void* pos, 
   if (rc) return rc;
   p.u = u; p.mem = mem; p.pos = pos; p.kpm = key_pad; p.probs = probs; p.wavg = wavg; p.zext = zext;
   const int SP = (S + 3) & ~3;
-  const size_t lds = (size_t)(2 * QH * SP + 4 * QH * QE + QH) * sizeof(float);
-  TD_REQUIRE(lds <= 64 * 1024, "td_cross_q1_fwd: S=%d too large for LDS", S);
+  const size_t lds = (size_t)(2 * QH * SP + 4 * QH * QE + QH) * sizeof(float);  // (the resident VALU kernel: 53 KiB at CQ_RESIDENT_MAX rows)
   hipStream_t st = (hipStream_t)stream;
   const bool prof = prof_on();
   if (prof) {
@@ -866,7 +1493,11 @@ extern "C" int td_cross_q1_fwd(const void* u, const void* mem, const void* pos, 
   }
   // TD_CROSS_Q1_MFMA=0: the VALU kernel in bf16 too (A/B; the fp32 mode always runs it: exact-fp32 parity)
   static const int mfma_on = [] { const char* e_ = getenv("TD_CROSS_Q1_MFMA"); return e_ ? atoi(e_) : 1; }();
-  if (dtype == TD_BF16 && mfma_on && S <= 128) cross_q1_fwd_mfma_kernel<128><<<F, 512, 0, st>>>(p);
+  if (S > CQ_RESIDENT_MAX) {  // streaming instances: LDS use does not depend on S
+    if (dtype == TD_BF16 && mfma_on) cross_q1_fwd_stream_mfma_kernel<<<F, 512, 0, st>>>(p);
+    else if (dtype == TD_BF16) cross_q1_fwd_stream_kernel<u16><<<F, 256, 0, st>>>(p);
+    else cross_q1_fwd_stream_kernel<float><<<F, 256, 0, st>>>(p);
+  } else if (dtype == TD_BF16 && mfma_on && S <= 128) cross_q1_fwd_mfma_kernel<128><<<F, 512, 0, st>>>(p);
   else if (dtype == TD_BF16 && mfma_on && S <= 160) cross_q1_fwd_mfma_kernel<160><<<F, 512, 0, st>>>(p);
   else if (dtype == TD_BF16 && mfma_on && S <= 256) cross_q1_fwd_mfma_kernel<256><<<F, 512, 0, st>>>(p);
   else if (dtype == TD_BF16) cross_q1_fwd_kernel<u16><<<F, 256, lds, st>>>(p);
@@ -890,8 +1521,7 @@ static int cross_q1_bwd_launch(const void* u, const void* mem, const void* pos, 
   p.accumulate = (accumulate && d_mem) ? 1 : 0;
   p.coef = (u16*)coef; p.coef_ld = coef_ld; p.coef_col = coef_col;
   const int SP = (S + 3) & ~3;
-  const size_t lds = (size_t)(3 * QH * SP + 4 * QH * QE) * sizeof(float);
-  TD_REQUIRE(lds <= 64 * 1024, "%s: S=%d too large for LDS", who, S);
+  const size_t lds = (size_t)(3 * QH * SP + 4 * QH * QE) * sizeof(float);  // (the resident VALU kernel: 62 KiB at CQ_RESIDENT_MAX rows)
   hipStream_t st = (hipStream_t)stream;
   const bool prof = prof_on();
   if (prof) {
@@ -903,7 +1533,11 @@ static int cross_q1_bwd_launch(const void* u, const void* mem, const void* pos, 
   // the matrix-pipe kernel serves the bf16 launches that do not touch an fp32 d(memory) (deferred, or not wanted): 92 us against 129 us
   // for the VALU kernel in the same mode at 1 600 frames x 151 rows (212 us with the fp32 read-modify-write).  TD_CROSS_Q1_MFMA=0: off
   static const int mfma_on = [] { const char* e_ = getenv("TD_CROSS_Q1_MFMA"); return e_ ? atoi(e_) : 1; }();
-  if (dtype == TD_BF16 && mfma_on && !d_mem && S <= 128) cross_q1_bwd_mfma_kernel<128><<<F, 512, 0, st>>>(p);
+  if (S > CQ_RESIDENT_MAX) {  // streaming instances; an fp32 d(memory) keeps bf16 launches on the VALU family here too
+    if (dtype == TD_BF16 && mfma_on && !d_mem) cross_q1_bwd_stream_mfma_kernel<<<F, 512, 0, st>>>(p);
+    else if (dtype == TD_BF16) cross_q1_bwd_stream_kernel<u16><<<F, 256, 0, st>>>(p);
+    else cross_q1_bwd_stream_kernel<float><<<F, 256, 0, st>>>(p);
+  } else if (dtype == TD_BF16 && mfma_on && !d_mem && S <= 128) cross_q1_bwd_mfma_kernel<128><<<F, 512, 0, st>>>(p);
   else if (dtype == TD_BF16 && mfma_on && !d_mem && S <= 160) cross_q1_bwd_mfma_kernel<160><<<F, 512, 0, st>>>(p);
   else if (dtype == TD_BF16 && mfma_on && !d_mem && S <= 256) cross_q1_bwd_mfma_kernel<256><<<F, 512, 0, st>>>(p);
   else if (dtype == TD_BF16) cross_q1_bwd_kernel<u16><<<F, 256, lds, st>>>(p);

@@ -160,7 +160,9 @@ class TransformerDecoder(nn.Module):
         # and the memory rows are never projected (functional.CrossQ1Fn).  TD_CROSS_Q1=0 (A/B), learned position embeddings (pos
         # needs a gradient) or another width / head count: the projected-memory path, hoisted over the layers (TD_KV_HOIST=0: per layer).
         att = self.layers[0].cross_attn_image
-        if (os.environ.get("TD_CROSS_Q1", "1") != "0" and att.embed_dim == 256 and att.num_heads == 8 and S <= 320  # (S: the frame core's LDS budget)
+        # Any S: up to 320 rows per frame the frame core keeps the frame in LDS, beyond it streams the rows in chunks (csrc/cross_attn.hip);
+        # profiles/cross_q1_tokens.log: the group is 5.1x / 5.1x / 6.2x faster than the projected one at S = 391 / 553 / 1 080 - no crossover to gate on.
+        if (os.environ.get("TD_CROSS_Q1", "1") != "0" and att.embed_dim == 256 and att.num_heads == 8
                 and not (pos is not None and pos.requires_grad)):
             kv = Fk.cross_q1_memory(mem, pos)
         else:
