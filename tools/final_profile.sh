@@ -30,7 +30,6 @@ kill $SMI 2>/dev/null
 V="--steps 10 --warmup 3 --cpu-frames 0 --roofline-steps 0 --dedupe-steps 0"
 timeout 600 python bench.py $V > $O/${tag}_bench_variant_default.json 2>/dev/null
 TD_CHAIN=0 timeout 600 python bench.py $V > $O/${tag}_bench_variant_chain_off.json 2>/dev/null     # layer3's conv3 -> next conv1 as two launches again
-TD_WGRAD_WIDE4=1 timeout 600 python bench.py $V > $O/${tag}_bench_variant_wgrad_wide4.json 2>/dev/null  # weight gradients on four-wavefront 128 x 128 wave tiles
 timeout 600 python bench.py $V > $O/${tag}_bench_variant_default_2.json 2>/dev/null
 TD_CHAIN=0 timeout 600 python bench.py $V > $O/${tag}_bench_variant_chain_off_2.json 2>/dev/null
 TD_CONV_BIG_PERSIST=0 timeout 600 python bench.py $V > $O/${tag}_bench_variant_big8_one_tile_per_workgroup.json 2>/dev/null

@@ -21,9 +21,6 @@
 #include <algorithm>
 #include <vector>
 
-#ifndef TD_WGRAD_EARLY_ISSUE
-#define TD_WGRAD_EARLY_ISSUE 1  // wide weight gradients: a stage buffer is refilled as soon as it is free, one whole stage ahead of its wait (0: half a stage; A/B builds)
-#endif
 #ifndef TD_BIG_XCD_CONTIG
 #define TD_BIG_XCD_CONTIG 1  // conv_gemm_big8_kernel: an XCD walks a contiguous range of row tiles (0: row tile = 8 * seq + XCD; A/B builds)
 #endif
@@ -1535,10 +1532,10 @@ __device__ __forceinline__ int wg_swz(int row) {
   return ES == 2 ? ((row & 3) | (((row >> 3) & 1) << 2)) : (row & 7);
 }
 
-// NSTG = 2: two 32-KiB stages, one in flight, two workgroups per CU.  NSTG = 4: four stages (128 KiB of the CU's 160 KiB
-// LDS, one workgroup per CU), three in flight behind counted s_waitcnt vmcnt - the launch has about one workgroup per
-// CU anyway (fp32 atomics per output tile limit the split count), so bytes in flight per CU are what is left to raise.
-template <typename T, int NSTG, bool PW>
+// Four 32-KiB stages (128 KiB of the CU's 160 KiB LDS, one workgroup per CU), three in flight behind counted
+// s_waitcnt vmcnt - the launch has about one workgroup per CU anyway (fp32 atomics per output tile limit the split
+// count), so bytes in flight per CU are what is left to raise.
+template <typename T, bool PW>
 __device__ __forceinline__ void wgrad_body(const WgradParams& p, const int bx, const int by, const int bz, const int lin) {
   constexpr int ES = sizeof(T);
   constexpr int VEC = 16 / ES;
@@ -1552,8 +1549,8 @@ __device__ __forceinline__ void wgrad_body(const WgradParams& p, const int bx, c
   constexpr uint32_t OOB = 0xFFFFFFF0u;
   __shared__ __attribute__((aligned(16))) char stage0[2 * TILEB];
   __shared__ __attribute__((aligned(16))) char stage1[2 * TILEB];
-  __shared__ __attribute__((aligned(16))) char stage2[NSTG == 4 ? 2 * TILEB : 16];
-  __shared__ __attribute__((aligned(16))) char stage3[NSTG == 4 ? 2 * TILEB : 16];
+  __shared__ __attribute__((aligned(16))) char stage2[2 * TILEB];
+  __shared__ __attribute__((aligned(16))) char stage3[2 * TILEB];
 
   const td_conv_desc& d = p.d;
   const int t = threadIdx.x;
@@ -1716,39 +1713,26 @@ __device__ __forceinline__ void wgrad_body(const WgradParams& p, const int bx, c
 #define TD_WSTAMP(i) do { if (stp && t == 0) stp[i] = __builtin_readcyclecounter(); } while (0)
   if (stp && t == 0) stp[0] = t_start;
   TD_WSTAMP(1);
-  if constexpr (NSTG == 2) {
-    issue_stage(stage0);
-    for (int it = 0; it < nit; it += 2) {
-      __syncthreads();
-      if (it + 1 < nit) issue_stage(stage1);
-      compute_stage(stage0);
-      if (it + 1 >= nit) break;
-      __syncthreads();
-      if (it + 2 < nit) issue_stage(stage0);
-      compute_stage(stage1);
-    }
-  } else {
-    // every step issues exactly one stage (rows past mend are all-OOB = zero fill, no traffic), so "the stage I am about
-    // to read has landed" is always "at most two stages = 4*LI DMA instructions of this wave still outstanding"
+  // every step issues exactly one stage (rows past mend are all-OOB = zero fill, no traffic), so "the stage I am about
+  // to read has landed" is always "at most two stages = 4*LI DMA instructions of this wave still outstanding"
 #define TD_WG_STEP(cur, nxt, j)                                                        \
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * LI) : "memory");                      \
   __builtin_amdgcn_s_barrier();                                                       \
   issue_stage(nxt);                                                                   \
   if ((j) >= 0) { compute_stage(cur); if ((j) < 32) TD_WSTAMP(4 + (j)); }
-    // software-pipeline warm-up folded into the loop (steps -3..-1 only issue): every stage buffer has exactly one
-    // static DMA site, which keeps the compiler's own LDS-DMA wait counts exact
-    for (int it = -3; it < nit; it += 4) {
-      TD_WG_STEP(stage1, stage0, it)
-      if (it + 1 >= nit) break;
-      TD_WG_STEP(stage2, stage1, it + 1)
-      if (it + 2 >= nit) break;
-      TD_WG_STEP(stage3, stage2, it + 2)
-      if (it + 3 >= nit) break;
-      TD_WG_STEP(stage0, stage3, it + 3)
-    }
-#undef TD_WG_STEP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing zero-fill DMAs must not outlive the workgroup's LDS
+  // software-pipeline warm-up folded into the loop (steps -3..-1 only issue): every stage buffer has exactly one
+  // static DMA site, which keeps the compiler's own LDS-DMA wait counts exact
+  for (int it = -3; it < nit; it += 4) {
+    TD_WG_STEP(stage1, stage0, it)
+    if (it + 1 >= nit) break;
+    TD_WG_STEP(stage2, stage1, it + 1)
+    if (it + 2 >= nit) break;
+    TD_WG_STEP(stage3, stage2, it + 2)
+    if (it + 3 >= nit) break;
+    TD_WG_STEP(stage0, stage3, it + 3)
   }
+#undef TD_WG_STEP
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing zero-fill DMAs must not outlive the workgroup's LDS
   // D[i=co][j=kk]: lane holds co = base + 4*lg + r, kk = base + lr
   TD_WSTAMP(2);
   if (do_bias && wx == 0 && lr == 0) {
@@ -1801,9 +1785,9 @@ __device__ __forceinline__ void wgrad_body(const WgradParams& p, const int bx, c
 #undef TD_WSTAMP
 }
 
-template <typename T, int NSTG, bool PW>
-__global__ __launch_bounds__(256, NSTG == 2 ? 2 : 1) void conv_wgrad_kernel(WgradParams p) {
-  wgrad_body<T, NSTG, PW>(p, blockIdx.x, blockIdx.y, blockIdx.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+template <typename T, bool PW>
+__global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(WgradParams p) {
+  wgrad_body<T, PW>(p, blockIdx.x, blockIdx.y, blockIdx.z, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
 }
 
 // Batched form: one launch covers the weight gradients of many layers.  With every trainable conv of the trunk in one
@@ -1818,8 +1802,8 @@ struct WgradXcdIndex {
   int slots[8];  // work items of XCD x
 };
 
-template <typename T, int NSTG, bool PW>
-__global__ __launch_bounds__(256, NSTG == 2 ? 2 : 1) void conv_wgrad_batch_kernel(const WgradParams* __restrict__ jobs, WgradXcdIndex xi) {
+template <typename T, bool PW>
+__global__ __launch_bounds__(256, 1) void conv_wgrad_batch_kernel(const WgradParams* __restrict__ jobs, WgradXcdIndex xi) {
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   if (slot >= xi.slots[xcd]) return;
   int lo = xi.start[xcd], hi = xi.start[xcd + 1] - 1;
@@ -1833,7 +1817,7 @@ __global__ __launch_bounds__(256, NSTG == 2 ? 2 : 1) void conv_wgrad_batch_kerne
   const int bx = local % p.tn;
   local /= p.tn;
   const int by = local % p.tk;
-  wgrad_body<T, NSTG, PW>(p, bx, by, local / p.tk, blockIdx.x);
+  wgrad_body<T, PW>(p, bx, by, local / p.tk, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1851,17 +1835,14 @@ __global__ __launch_bounds__(256, NSTG == 2 ? 2 : 1) void conv_wgrad_batch_kerne
 // filter tap - validity, tap and channel base are wave-uniform scalars, the lane only adds its column.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// NW = 8 (round 6, TD_WGRAD_WIDE8): the same tile on EIGHT wavefronts, two per SIMD - wave tiles of 128 x 64 (256-channel layers) instead
-// of 64 x 64: 12 instead of 16 transposing fragment reads per 32 MFMAs, two DMA instructions per wavefront, sub-tile and stage.
-template <int GS, int XS, bool PW, int NW = 16>
+template <int GS, int XS, bool PW>
 __device__ __forceinline__ void wgrad_wide_body(const WgradParams& p, const int bx, const int by, const int bz, char* st0, char* st1) {
   constexpr int ES = 2, MK = 64, ROWB = 256, SUB = MK * ROWB;  // one 128-column sub-tile = 16 KiB
-  static_assert(NW == 16 || NW == 8, "four or two wavefronts per SIMD");
-  constexpr int RPW = 16 / NW;                 // DMA instructions (4 rows each) per wavefront, sub-tile and stage
-  constexpr int WVK = XS * 2, WVC = NW / WVK;  // wavefronts along k / along the output channels
-  constexpr int WCO = GS * 128 / WVC;
+  constexpr int RPW = 1;  // DMA instructions (4 rows each) per wavefront, sub-tile and stage.  (The one-trip loops over it stay as loops: written out as
+                          // scalars, the same arithmetic comes out of the compiler in another instruction order, and this kernel's schedule is measured.)
+  constexpr int WVK = XS * 2, WVC = 16 / WVK;  // wavefronts along k / along the output channels
+  constexpr int WCO = GS * 128 / WVC;          // output channels per wavefront: 64 or 32
   constexpr int FI = WCO / 16, FJ = 4;
-  static_assert(FI >= 1 && WCO <= 128, "wave tile");
   constexpr uint32_t OOB = 0xFFFFFFF0u;
   const td_conv_desc& d = p.d;
   const int t = threadIdx.x;
@@ -1874,9 +1855,8 @@ __device__ __forceinline__ void wgrad_wide_body(const WgradParams& p, const int 
   const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.g_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, p.src_bytes, 0x00020000);
 
-  // DMA bookkeeping: this wavefront's instruction h fills rows (wave * RPW + h) * 4 + lane/16 of every sub-tile, LDS chunk lane%16
-  // (the swizzle of a row depends on its bits 0, 1 and 3: the same for both instructions of a wavefront)
-  const int drow = wave * (4 * RPW) + (lane >> 4);
+  // DMA bookkeeping: this wavefront's instruction fills rows wave * 4 + lane/16 of every sub-tile, LDS chunk lane%16
+  const int drow = wave * 4 + (lane >> 4);
   const int c16 = lane & 15;
   const int col = ((((c16 >> 1) ^ wg_swz<ES>(drow)) << 1) | (c16 & 1)) * 8;  // logical column of this lane's chunk
   int mcur = mbeg + drow;
@@ -1963,7 +1943,7 @@ __device__ __forceinline__ void wgrad_wide_body(const WgradParams& p, const int 
     return u32x4{l2.x, l2.y, h2.x, h2.y};
   };
   auto load_frags = [&](const char* st, int ks) {
-    const int xoff = wxk * 64, goff = wyc * WCO;  // both inside one sub-tile (WCO <= 64 or 128-aligned)
+    const int xoff = wxk * 64, goff = wyc * WCO;  // both inside one sub-tile (WCO <= 64)
     // the swizzle operand is laundered per call: the 2 x (FI + FJ) fragment addresses are then recomputed where they are
     // used (an xor and a shift-add in the shadow of the MFMAs) instead of living in 16 registers across the loop
     asm volatile("" : "+v"(f));
@@ -1983,7 +1963,6 @@ __device__ __forceinline__ void wgrad_wide_body(const WgradParams& p, const int 
       for (int j = 0; j < FJ; ++j)
         asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(gf[i]), "v"(xf[j]));
   };
-#if TD_WGRAD_EARLY_ISSUE
   // Round 6: the refill of a stage buffer is issued the moment the buffer is free - behind the barrier that follows its last fragment
   // read, i.e. in the middle of the stage that consumed it, for the stage AFTER the next one - and waited for one whole stage later.
   // (Rounds 4 - 5 issued it at the head of the next stage and waited for it in that stage's middle: half a stage, ~0.5 us, of lead for a
@@ -2001,38 +1980,20 @@ __device__ __forceinline__ void wgrad_wide_body(const WgradParams& p, const int 
     mfmas();
     __builtin_amdgcn_sched_barrier(0);
   };
-#else
-  auto stage_body = [&](char* cur, char* nxt) {
-    issue_stage(nxt);  // every wavefront finished reading `nxt` before the last barrier; past the slice: all-OOB, no traffic
-    load_frags(cur, 0);
-    __builtin_amdgcn_sched_barrier(0);  // (the scheduler would hoist the second k-step's reads: 2 x 32 fragment registers)
-    mfmas();
-    __builtin_amdgcn_sched_barrier(0);
-    load_frags(cur, 1);
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0): own DMA of the next stage landed, own reads of `cur` returned
-    __builtin_amdgcn_s_barrier();
-    mfmas();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-#endif
 
   // ONE loop over stage pairs and nothing else: an odd stage count is rounded up (rows past the slice are zero-filled
   // without traffic).  A separate tail would bring register spills of the accumulators, and a spill store right behind an
   // inline-asm MFMA lacks the MFMA -> VMEM wait states the compiler adds for MFMAs it knows about.
   const int npair = ((mend - mbeg + MK - 1) / MK + 1) / 2;
   issue_stage(st0);
-#if TD_WGRAD_EARLY_ISSUE
   issue_stage(st1);
-#endif
   __syncthreads();
 #pragma unroll 1
   for (int it = 0; it < npair; ++it) {
     stage_body(st0, st1);
     stage_body(st1, st0);
   }
-#if TD_WGRAD_EARLY_ISSUE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the two trailing (all-OOB) refills must not outlive the workgroup's LDS
-#endif
   // last MFMA results -> first read: 2 x 16 idle cycles, and every accumulator passes through an asm "modification" placed
   // behind them, so no compiler-generated use (VALU read, spill store) of an accumulator can be scheduled before the wait
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -2090,267 +2051,6 @@ __global__ __launch_bounds__(1024, 1) void conv_wgrad_wide_batch_kernel(const Wg
     case 1: wgrad_wide_body<2, 1, false>(p, bx, by, bz, wst0, wst1); break;
     default: wgrad_wide_body<2, 1, true>(p, bx, by, bz, wst0, wst1); break;
   }
-}
-
-// the same launch on eight wavefronts per workgroup (TD_WGRAD_WIDE8=1; see wgrad_wide_body)
-__global__ __launch_bounds__(512, 1) void conv_wgrad_wide8_batch_kernel(const WgradParams* __restrict__ jobs, WgradXcdIndex xi) {
-  __shared__ __attribute__((aligned(16))) char wst0[65536];
-  __shared__ __attribute__((aligned(16))) char wst1[65536];
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  if (slot >= xi.slots[xcd]) return;
-  int lo = xi.start[xcd], hi = xi.start[xcd + 1] - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].first <= slot) lo = mid;
-    else hi = mid - 1;
-  }
-  const WgradParams p = jobs[lo];
-  int local = slot - p.first;
-  const int bx = local % p.tn;
-  local /= p.tn;
-  const int by = local % p.tk, bz = local / p.tk;
-  switch (p.cls) {
-    case 3: wgrad_wide_body<2, 2, false, 8>(p, bx, by, bz, wst0, wst1); break;
-    case 7: wgrad_wide_body<2, 2, true, 8>(p, bx, by, bz, wst0, wst1); break;
-    case 2: wgrad_wide_body<1, 2, false, 8>(p, bx, by, bz, wst0, wst1); break;
-    case 6: wgrad_wide_body<1, 2, true, 8>(p, bx, by, bz, wst0, wst1); break;
-    case 1: wgrad_wide_body<2, 1, false, 8>(p, bx, by, bz, wst0, wst1); break;
-    default: wgrad_wide_body<2, 1, true, 8>(p, bx, by, bz, wst0, wst1); break;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// 256 x 256 weight-gradient tiles on FOUR wavefronts with 128 x 128 wave tiles (round 6; the 256-channel / K >= 256 jobs of the batched launch:
-// most of the trunk's weight-gradient FLOPs).  Why: both operands of dW = g^T x are reduction-major in HBM, so every MFMA fragment is a pair
-// of transposing LDS reads (ds_read_b64_tr_b16), and those sustain 85 - 119 B/clk per CU here (round 4).  A 64 x 64 wave tile (the sixteen-
-// wavefront body above) needs 16 such reads per 16 MFMAs = 128 B/clk at the full matrix rate - the kernel sat at mfma_util 0.39.  A 128 x 128
-// wave tile reads 16 fragments (32 reads) per 64 MFMAs: 64 B/clk.  Price: one wavefront per SIMD (256 accumulator AGPRs, allocated by hand as in
-// chain.hip), so the next stage's fragments are read UNDER this stage's MFMAs into a second register set - two fragments behind every eight MFMAs.
-// Stages are 32 reduction rows (one K-step; 4 sub-tiles x 8 KiB) on a ring of four: the barrier at the top of stage s publishes stage s + 1
-// (whose fragments are read during stage s) and frees the buffer of stage s - 1 for stage s + 3.  Same LDS image per sub-tile and the same
-// summation order per output element as the sixteen-wavefront body: results are bit-identical to it for unsplit jobs.
-template <bool PW>
-__device__ __forceinline__ void wgrad_wide4_body(const WgradParams& p, const int bx, const int by, const int bz, char* r0_, char* r1_, char* r2_, char* r3_) {
-  constexpr int ES = 2, MK = 32, ROWB = 256, SUB = MK * ROWB;  // one 128-column sub-tile of a stage = 8 KiB; a stage = g0 g1 x0 x1
-  constexpr uint32_t OOB = 0xFFFFFFF0u;
-  const td_conv_desc& d = p.d;
-  const int t = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
-  const int co0 = bx * 256, kk0 = by * 256;
-  const int mbeg = bz * p.mper;
-  const int mend = min(p.M, mbeg + p.mper);
-  if (mbeg >= mend) return;
-  const int HoWo = d.Ho * d.Wo;
-  const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.g_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, p.src_bytes, 0x00020000);
-  asm volatile("" ::: "a255");  // the whole accumulator file is this kernel's: acc(i, j) = a[4 (8 i + j) .. + 4], i = output-channel fragment, j = k fragment
-
-  // DMA bookkeeping: piece e (0, 1) of this wavefront fills rows (e * 4 + wave) * 4 + lane / 16 of every sub-tile, LDS chunk lane % 16
-  const int c16 = lane & 15;
-  int mcur[2], rn[2], rho[2], rwo[2], col[2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int drow = (e * 4 + wave) * 4 + (lane >> 4);
-    col[e] = ((((c16 >> 1) ^ wg_swz<ES>(drow)) << 1) | (c16 & 1)) * 8;  // logical column of this lane's chunk
-    mcur[e] = mbeg + drow;
-    rn[e] = mcur[e] / HoWo;
-    rho[e] = (mcur[e] - rn[e] * HoWo) / d.Wo;
-    rwo[e] = mcur[e] - rn[e] * HoWo - rho[e] * d.Wo;
-  }
-  bool g_in[2], x_in[2];
-  int g_c0[2], x_c0[2], x_r[2], x_s[2];
-#pragma unroll
-  for (int s_ = 0; s_ < 2; ++s_) {
-    g_c0[s_] = co0 + s_ * 128;
-    g_in[s_] = g_c0[s_] < d.Nc;
-    const int kk = kk0 + s_ * 128;
-    x_in[s_] = kk < p.K;
-    x_r[s_] = 0; x_s[s_] = 0; x_c0[s_] = kk;
-    if (!PW && d.R * d.S > 1) {
-      const int tap = kk / d.C;
-      x_c0[s_] = kk - tap * d.C;
-      x_r[s_] = tap / d.S;
-      x_s[s_] = tap - x_r[s_] * d.S;
-    }
-  }
-  const int dN = MK / HoWo, dH = (MK - dN * HoWo) / d.Wo, dW = MK - dN * HoWo - dH * d.Wo;
-  // 8 pieces per stage, BRANCH-FREE (all-ones / all-zeros masks, no bool select the compiler could turn into divergent control flow: a piece
-  // issued once per side of a branch would break the counted waits and leave LDS slots unwritten).  Rows past the slice, columns past the
-  // matrix and out-of-image taps: out-of-range offset = zero fill, no traffic.
-  auto neg = [](int v) -> uint32_t { return (uint32_t)(v >> 31); };  // all ones if v < 0
-  uint32_t gm[2], xm[2];
-#pragma unroll
-  for (int s_ = 0; s_ < 2; ++s_) {
-    gm[s_] = g_in[s_] ? 0xFFFFFFFFu : 0u;
-    xm[s_] = x_in[s_] ? 0xFFFFFFFFu : 0u;
-  }
-  auto issue_stage = [&](char* st) {
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int m = mcur[e];
-      const uint32_t okm = neg(m - mend);  // m < mend
-      const uint32_t grow = ((uint32_t)m * (uint32_t)p.ldg + (uint32_t)col[e]) * ES;
-#pragma unroll
-      for (int s_ = 0; s_ < 2; ++s_) {
-        const uint32_t k_ = okm & gm[s_];
-        const uint32_t og = ((grow + (uint32_t)g_c0[s_] * ES) & k_) | (OOB & ~k_);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_g, (lds_ptr_t)(st + s_ * SUB + (e * 4 + wave) * 1024), 16, og, 0, 0, 0);
-      }
-#pragma unroll
-      for (int s_ = 0; s_ < 2; ++s_) {
-        uint32_t ox, k_;
-        if constexpr (PW) {
-          k_ = okm & xm[s_];
-          ox = ((uint32_t)m * (uint32_t)d.C + (uint32_t)(x_c0[s_] + col[e])) * ES;
-        } else {
-          const int hs = rho[e] * d.stride - d.pad + x_r[s_], ws = rwo[e] * d.stride - d.pad + x_s[s_];
-          k_ = okm & xm[s_] & ~neg(hs | (d.Hs - 1 - hs) | ws | (d.Ws - 1 - ws));  // 0 <= hs < Hs and 0 <= ws < Ws
-          ox = ((uint32_t)((rn[e] * d.Hs + hs) * d.Ws + ws) * (uint32_t)d.C + (uint32_t)(x_c0[s_] + col[e])) * ES;
-        }
-        ox = (ox & k_) | (OOB & ~k_);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_ptr_t)(st + (2 + s_) * SUB + (e * 4 + wave) * 1024), 16, ox, 0, 0, 0);
-      }
-      if constexpr (!PW) {
-        rwo[e] += dW;
-        const int c1 = (int)(~neg(rwo[e] - d.Wo) & 1u);  // rwo >= Wo
-        rwo[e] -= c1 * d.Wo;
-        rho[e] += dH + c1;
-        const int c2 = (int)(~neg(rho[e] - d.Ho) & 1u);
-        rho[e] -= c2 * d.Ho;
-        rn[e] += dN + c2;
-      }
-      mcur[e] += MK;
-    }
-  };
-
-  const int wyc = wave >> 1, wxk = wave & 1;  // this wavefront's 128 output channels / 128 k columns = sub-tile wyc of g, sub-tile wxk of x
-  const int lr = lane & 15, lg = lane >> 4;
-  const int jrow = lr >> 2, q = lr & 3;
-  const int f = jrow | ((lg & 1) << 2);  // = wg_swz(r0) = wg_swz(r0 + 4)
-  const int rowoff = (8 * lg + jrow) * ROWB + q * 8;
-  // fragment F (0..7 = g blocks, 8..15 = x blocks) of the stage in buffer `st`: two transposing reads (rows r0, r0 + 4)
-  auto frag = [&](const char* st, int F) -> u32x4 {
-    const char* sub = st + (F < 8 ? wyc : 2 + wxk) * SUB;
-    const int cb = (((F & 7) ^ f) << 5);
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(sub + rowoff + cb));
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(sub + rowoff + 4 * ROWB + cb));
-    const uint2 l2 = *(uint2*)&lo, h2 = *(uint2*)&hi;
-    return u32x4{l2.x, l2.y, h2.x, h2.y};
-  };
-  u32x4 fa[16], fb[16];  // the two fragment sets: [0..7] g (output channels), [8..15] x (k columns)
-
-  // one stage: 64 MFMAs on set `cur`; the next stage's 16 fragments are read into set `nxt` two at a time behind every eight MFMAs
-#define TD_W4_MFMA(I, Jx, cur) asm volatile("v_mfma_f32_16x16x32_bf16 a[%c0:%c1], %2, %3, a[%c0:%c1]" ::"n"(4 * (8 * (I) + (Jx))), "n"(4 * (8 * (I) + (Jx)) + 3), "v"(cur[I]), "v"(cur[8 + (Jx)]));
-#define TD_W4_ROWM(I, cur) TD_W4_MFMA(I, 0, cur) TD_W4_MFMA(I, 1, cur) TD_W4_MFMA(I, 2, cur) TD_W4_MFMA(I, 3, cur) TD_W4_MFMA(I, 4, cur) TD_W4_MFMA(I, 5, cur) TD_W4_MFMA(I, 6, cur) TD_W4_MFMA(I, 7, cur)
-// (the x fragments - needed by EVERY row of the next stage - are read first, under rows 0..3; g fragment I, needed by row I, under rows 4..7;
-//  the pieces of stage s + 3 are issued behind row 3: the top of a stage is a wait and a barrier only)
-#define TD_W4_STAGE(cur, nxt, nbuf, buf_sp3)                                                            \
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                                                      \
-  __builtin_amdgcn_s_barrier();                                                                         \
-  TD_W4_ROWM(0, cur) nxt[8] = frag(nbuf, 8);   nxt[9] = frag(nbuf, 9);   __builtin_amdgcn_sched_barrier(0); \
-  TD_W4_ROWM(1, cur) nxt[10] = frag(nbuf, 10); nxt[11] = frag(nbuf, 11); __builtin_amdgcn_sched_barrier(0); \
-  TD_W4_ROWM(2, cur) nxt[12] = frag(nbuf, 12); nxt[13] = frag(nbuf, 13); __builtin_amdgcn_sched_barrier(0); \
-  TD_W4_ROWM(3, cur) nxt[14] = frag(nbuf, 14); nxt[15] = frag(nbuf, 15); __builtin_amdgcn_sched_barrier(0); \
-  issue_stage(buf_sp3);                                                                                 \
-  __builtin_amdgcn_sched_barrier(0);                                                                    \
-  TD_W4_ROWM(4, cur) nxt[0] = frag(nbuf, 0);  nxt[1] = frag(nbuf, 1);   __builtin_amdgcn_sched_barrier(0); \
-  TD_W4_ROWM(5, cur) nxt[2] = frag(nbuf, 2);  nxt[3] = frag(nbuf, 3);   __builtin_amdgcn_sched_barrier(0); \
-  TD_W4_ROWM(6, cur) nxt[4] = frag(nbuf, 4);  nxt[5] = frag(nbuf, 5);   __builtin_amdgcn_sched_barrier(0); \
-  TD_W4_ROWM(7, cur) nxt[6] = frag(nbuf, 6);  nxt[7] = frag(nbuf, 7);   __builtin_amdgcn_sched_barrier(0);
-  // top of stage s: this wavefront's pieces of stage s + 1 have landed (behind them: the 8 pieces of stage s + 2), then everybody's; the
-  // buffer of stage s - 1 (read during stage s - 2, consumed in stage s - 1) takes stage s + 3 from the middle of the stage on
-
-  // zero the accumulator file (64 fragments): C = 0 forms would need a first-stage copy of the whole stage macro
-#define TD_W4_Z(N) asm volatile("v_accvgpr_write_b32 a%c0, 0\n\tv_accvgpr_write_b32 a%c1, 0\n\tv_accvgpr_write_b32 a%c2, 0\n\tv_accvgpr_write_b32 a%c3, 0" ::"n"(4 * (N)), "n"(4 * (N) + 1), "n"(4 * (N) + 2), "n"(4 * (N) + 3));
-#define TD_W4_Z8(B) TD_W4_Z(B) TD_W4_Z(B + 1) TD_W4_Z(B + 2) TD_W4_Z(B + 3) TD_W4_Z(B + 4) TD_W4_Z(B + 5) TD_W4_Z(B + 6) TD_W4_Z(B + 7)
-  TD_W4_Z8(0) TD_W4_Z8(8) TD_W4_Z8(16) TD_W4_Z8(24) TD_W4_Z8(32) TD_W4_Z8(40) TD_W4_Z8(48) TD_W4_Z8(56)
-#undef TD_W4_Z8
-#undef TD_W4_Z
-
-  const int nst = (mend - mbeg + MK - 1) / MK;
-  const int nquad = (nst + 3) / 4;  // ONE loop over stage quadruples and nothing else (extra stages: zero fill without traffic)
-  issue_stage(r0_);
-  issue_stage(r1_);
-  issue_stage(r2_);
-  asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // stage 0 has landed
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int F = 0; F < 16; ++F) fa[F] = frag(r0_, F);
-#pragma unroll 1
-  for (int it = 0; it < nquad; ++it) {
-    TD_W4_STAGE(fa, fb, r1_, r3_)
-    TD_W4_STAGE(fb, fa, r2_, r0_)
-    TD_W4_STAGE(fa, fb, r3_, r1_)
-    TD_W4_STAGE(fb, fa, r0_, r2_)
-  }
-#undef TD_W4_STAGE
-#undef TD_W4_ROWM
-#undef TD_W4_MFMA
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // trailing zero-fill DMAs / fragment reads must not outlive the workgroup's LDS
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");           // the asm MFMAs' results are read below
-  // D[i = co][j = kk]: lane holds co = base + 4 lg + rr, kk = base + lr
-  const int RS = d.R * d.S;
-  // (a wide job has Nc % 256 == 0 - host-checked - so every output channel of the tile exists; k columns past K and padded input channels do not)
-  float sc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) sc[i][rr] = p.scale ? p.scale[co0 + wyc * 128 + i * 16 + 4 * lg + rr] : 1.f;
-  const bool plain = p.out_mode == 2;  // (uniform) a single split: this workgroup owns the tile
-#define TD_W4_OUT(I, Jx)                                                                                                                     \
-  if (jok[Jx]) {                                                                                                                            \
-    float v_[4];                                                                                                                            \
-    asm volatile("v_accvgpr_read_b32 %0, a%c4\n\tv_accvgpr_read_b32 %1, a%c5\n\tv_accvgpr_read_b32 %2, a%c6\n\tv_accvgpr_read_b32 %3, a%c7"     \
-                 : "=v"(v_[0]), "=v"(v_[1]), "=v"(v_[2]), "=v"(v_[3])                                                                        \
-                 : "n"(4 * (8 * (I) + (Jx))), "n"(4 * (8 * (I) + (Jx)) + 1), "n"(4 * (8 * (I) + (Jx)) + 2), "n"(4 * (8 * (I) + (Jx)) + 3));      \
-    float* dst = jdst[Jx] + (size_t)((I) * 16) * cstride;                                                                                   \
-    _Pragma("unroll") for (int rr = 0; rr < 4; ++rr) {                                                                                      \
-      const float v = v_[rr] * sc[I][rr];                                                                                                   \
-      if (plain) dst[(size_t)rr * cstride] = v;                                                                                             \
-      else atomicAdd(dst + (size_t)rr * cstride, v);                                                                                        \
-    }                                                                                                                                       \
-  }
-  const size_t cstride = (size_t)p.ci_real * RS;  // elements between consecutive output channels of dW [Nc][ci_real][R][S]
-  bool jok[8];
-  float* jdst[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int kko = kk0 + wxk * 128 + j * 16 + lr;
-    int tap = 0, ci = kko;
-    if (!PW && RS > 1) {
-      tap = kko / d.C;
-      ci = kko - tap * d.C;
-    }
-    jok[j] = kko < p.K && ci < p.ci_real;
-    jdst[j] = p.dw + ((size_t)(co0 + wyc * 128 + 4 * lg) * p.ci_real + ci) * RS + tap;
-  }
-#define TD_W4_OUTROW(I) TD_W4_OUT(I, 0) TD_W4_OUT(I, 1) TD_W4_OUT(I, 2) TD_W4_OUT(I, 3) TD_W4_OUT(I, 4) TD_W4_OUT(I, 5) TD_W4_OUT(I, 6) TD_W4_OUT(I, 7)
-  TD_W4_OUTROW(0) TD_W4_OUTROW(1) TD_W4_OUTROW(2) TD_W4_OUTROW(3) TD_W4_OUTROW(4) TD_W4_OUTROW(5) TD_W4_OUTROW(6) TD_W4_OUTROW(7)
-#undef TD_W4_OUTROW
-#undef TD_W4_OUT
-}
-
-__global__ __launch_bounds__(256, 1) void conv_wgrad_wide4_batch_kernel(const WgradParams* __restrict__ jobs, WgradXcdIndex xi) {
-  // four 32-KiB stage buffers as four LDS objects: disjoint alias scopes, so the fragment reads of one stage do not wait for the LDS-DMA filling another
-  __shared__ __attribute__((aligned(1024))) char w4s0[32768];
-  __shared__ __attribute__((aligned(1024))) char w4s1[32768];
-  __shared__ __attribute__((aligned(1024))) char w4s2[32768];
-  __shared__ __attribute__((aligned(1024))) char w4s3[32768];
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  if (slot >= xi.slots[xcd]) return;
-  int lo = xi.start[xcd], hi = xi.start[xcd + 1] - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].first <= slot) lo = mid;
-    else hi = mid - 1;
-  }
-  const WgradParams p = jobs[lo];
-  int local = slot - p.first;
-  const int bx = local % p.tn;
-  local /= p.tn;
-  const int by = local % p.tk, bz = local / p.tk;
-  if (p.cls & 4) wgrad_wide4_body<true>(p, bx, by, bz, w4s0, w4s1, w4s2, w4s3);
-  else wgrad_wide4_body<false>(p, bx, by, bz, w4s0, w4s1, w4s2, w4s3);
 }
 
 static int validate(const td_conv_desc* d, int dtype, const char* who) {
@@ -2709,11 +2409,6 @@ extern "C" int td_linear_ex(const void* a1, const void* a2, const void* wmat, vo
   return check_launch("td_linear_ex");
 }
 
-static int wgrad_stages() {
-  static const int nstg = [] { const char* e = getenv("TD_WGRAD_STAGES"); return (e && atoi(e) == 2) ? 2 : 4; }();
-  return nstg;
-}
-
 // fills everything of p except the output fields; returns the split count through *splits_io.
 // auto_mode: 0 = single launch (about one workgroup per CU), > 0 = batched launch with work items of that many stages
 static int wgrad_fill(WgradParams& p, const void* g, const void* src, const td_conv_desc* d, int ldg, int dtype, int* splits_io,
@@ -2748,7 +2443,7 @@ static int wgrad_fill(WgradParams& p, const void* g, const void* src, const td_c
       // measured: 192-256 workgroups beat 512-1536 (fewer fp32 atomics per output tile)
       static const int target_blocks = [] { const char* e = getenv("TD_WGRAD_BLOCKS"); return e ? atoi(e) : 256; }();
       const int tiles = p.tn * p.tk;
-      splits = wgrad_stages() == 4 ? target_blocks / tiles : cdiv(target_blocks, tiles);  // 4 stages: one workgroup per CU, never a second round
+      splits = target_blocks / tiles;  // four stages take one workgroup per CU: never a second round
       const int maxs = cdiv(p.M, 8 * mk);
       if (splits > maxs) splits = maxs;
     } else {
@@ -2789,19 +2484,13 @@ extern "C" int td_conv_wgrad_bias(const void* g, const void* src, float* dw, flo
   if (prof) prof_begin(TD_PROF_WGRAD_SINGLE, dtype, 2.0 * p.M * d->Nc * p.K, st, p.M, d->Nc, p.K, d->R, d->stride, splits);
   if (prof) prof_set_bytes(((double)p.M * ldg + (double)d->N * d->Hs * d->Ws * d->C) * (dtype == TD_BF16 ? 2.0 : 4.0) + (double)d->Nc * p.K * 4.0);
   const bool pw = (d->R * d->S == 1) && d->stride == 1 && d->pad == 0;
-  const int nstg = wgrad_stages();
-#define TD_WG_LAUNCH(TT, NS)                                                    \
-  do {                                                                          \
-    if (pw) conv_wgrad_kernel<TT, NS, true><<<grid, 256, 0, st>>>(p);           \
-    else conv_wgrad_kernel<TT, NS, false><<<grid, 256, 0, st>>>(p);             \
+#define TD_WG_LAUNCH(TT)                                                    \
+  do {                                                                      \
+    if (pw) conv_wgrad_kernel<TT, true><<<grid, 256, 0, st>>>(p);           \
+    else conv_wgrad_kernel<TT, false><<<grid, 256, 0, st>>>(p);             \
   } while (0)
-  if (nstg == 4) {
-    if (dtype == TD_BF16) TD_WG_LAUNCH(u16, 4);
-    else TD_WG_LAUNCH(float, 4);
-  } else {
-    if (dtype == TD_BF16) TD_WG_LAUNCH(u16, 2);
-    else TD_WG_LAUNCH(float, 2);
-  }
+  if (dtype == TD_BF16) TD_WG_LAUNCH(u16);
+  else TD_WG_LAUNCH(float);
 #undef TD_WG_LAUNCH
   if (prof) prof_end(st);
   return check_launch("td_conv_wgrad");
@@ -2811,7 +2500,7 @@ extern "C" int td_conv_wgrad_bias(const void* g, const void* src, float* dw, flo
 // The job table of a launch lives in caller-provided memory: the library writes it into `table_host` (page-locked),
 // enqueues ONE hipMemcpyAsync into `table_dev` on the caller's stream and launches; no allocation, no synchronisation.
 static size_t wg_table_half(int n_jobs) { return (((size_t)n_jobs * sizeof(WgradParams)) + 255) & ~(size_t)255; }
-extern "C" size_t td_conv_wgrad_batch_table_bytes(int n_jobs) { return n_jobs > 0 ? 8 * wg_table_half(n_jobs) : 0; }  // (general / pointwise / wide-tile / four-wavefront wide-tile tables) x (overwriting / accumulating jobs)
+extern "C" size_t td_conv_wgrad_batch_table_bytes(int n_jobs) { return n_jobs > 0 ? 6 * wg_table_half(n_jobs) : 0; }  // (general / pointwise / wide-tile tables) x (overwriting / accumulating jobs)
 
 static int wgrad_batch_phase(const td_wgrad_job* jobs, int n_jobs, int dtype, void* table_host, void* table_dev, size_t half, bool accumulate, td_stream_t stream);
 
@@ -2827,16 +2516,14 @@ extern "C" int td_conv_wgrad_batch(const td_wgrad_job* jobs, int n_jobs, int dty
   int rc = TD_OK;
   if (!first.empty()) rc = wgrad_batch_phase(first.data(), (int)first.size(), dtype, table_host, table_dev, half, false, stream);
   if (rc == TD_OK && !second.empty())
-    rc = wgrad_batch_phase(second.data(), (int)second.size(), dtype, (char*)table_host + 4 * half, (char*)table_dev + 4 * half, half, true, stream);
+    rc = wgrad_batch_phase(second.data(), (int)second.size(), dtype, (char*)table_host + 3 * half, (char*)table_dev + 3 * half, half, true, stream);
   return rc;
 }
 
 static int wgrad_batch_phase(const td_wgrad_job* jobs, int n_jobs, int dtype, void* table_host, void* table_dev, size_t half, bool accumulate,
                              td_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
-  std::vector<WgradParams> tab[4];  // [0] general geometry, [1] pointwise, [2] wide tiles (conv_wgrad_wide_batch_kernel), [3] 256 x 256 tiles on four wavefronts (conv_wgrad_wide4_batch_kernel)
-  static const int wide8_on = [] { const char* e = getenv("TD_WGRAD_WIDE8"); return e ? atoi(e) : 0; }();  // the wide launch on eight wavefronts per workgroup (128 x 64 wave tiles)
-  static const int wide4_on = [] { const char* e = getenv("TD_WGRAD_WIDE4"); return e ? atoi(e) : 0; }();  // (measured 11 % SLOWER than the sixteen-wavefront tiles on the trunk's table, profiles/r06_wgrad_wide4.log: off by default, kept for the A/B and its bit-identity test)
+  std::vector<WgradParams> tab[3];  // [0] general geometry, [1] pointwise, [2] wide tiles (conv_wgrad_wide_batch_kernel)
   double flops = 0, abytes = 0;
   static const int wide_on = [] { const char* e = getenv("TD_WGRAD_WIDE"); return e ? atoi(e) : 1; }();
   static const int wide_min_m = [] { const char* e = getenv("TD_WGRAD_WIDE_MIN_M"); return e ? atoi(e) : 4096; }();
@@ -2888,7 +2575,7 @@ static int wgrad_batch_phase(const td_wgrad_job* jobs, int n_jobs, int dtype, vo
       p.tn = j.d.Nc / (gs * 128);
       p.tk = cdiv(p.K, xs * 128);
     }
-    tab[wide ? ((wide4_on && (p.cls & 3) == 3) ? 3 : 2) : (pw ? 1 : 0)].push_back(p);
+    tab[wide ? 2 : (pw ? 1 : 0)].push_back(p);
     flops += 2.0 * p.M * j.d.Nc * p.K;
     abytes += ((double)p.M * j.ldg + (double)j.d.N * j.d.Hs * j.d.Ws * j.d.C) * (dtype == TD_BF16 ? 2.0 : 4.0) + (double)j.d.Nc * j.ci_real * j.d.R * j.d.S * 4.0;
   }
@@ -2897,8 +2584,7 @@ static int wgrad_batch_phase(const td_wgrad_job* jobs, int n_jobs, int dtype, vo
     prof_begin(TD_PROF_WGRAD, dtype, flops, st, 0, 0, 0, 0, 0, n_jobs);
     prof_set_bytes(abytes);
   }
-  const int nstg = wgrad_stages();
-  for (int pw = 0; pw < 4; ++pw) {
+  for (int pw = 0; pw < 3; ++pw) {
     std::vector<WgradParams>& t = tab[pw];
     if (t.empty()) continue;
     // one XCD per job, longest job first onto the least loaded XCD; inside an XCD the long work items come first so
@@ -2957,23 +2643,14 @@ static int wgrad_batch_phase(const td_wgrad_job* jobs, int n_jobs, int dtype, vo
     }
     int rc;
     const unsigned grid = (unsigned)(8 * max_slots);
-#define TD_WGB_LAUNCH(TT, NS)                                                                \
-  do {                                                                                       \
-    if (pw) conv_wgrad_batch_kernel<TT, NS, true><<<grid, 256, 0, st>>>(dev, xi);            \
-    else conv_wgrad_batch_kernel<TT, NS, false><<<grid, 256, 0, st>>>(dev, xi);              \
+#define TD_WGB_LAUNCH(TT)                                                                \
+  do {                                                                                   \
+    if (pw) conv_wgrad_batch_kernel<TT, true><<<grid, 256, 0, st>>>(dev, xi);            \
+    else conv_wgrad_batch_kernel<TT, false><<<grid, 256, 0, st>>>(dev, xi);              \
   } while (0)
-    if (pw == 3) {
-      conv_wgrad_wide4_batch_kernel<<<grid, 256, 0, st>>>(dev, xi);
-    } else if (pw == 2) {
-      if (wide8_on) conv_wgrad_wide8_batch_kernel<<<grid, 512, 0, st>>>(dev, xi);
-      else conv_wgrad_wide_batch_kernel<<<grid, 1024, 0, st>>>(dev, xi);
-    } else if (nstg == 4) {
-      if (dtype == TD_BF16) TD_WGB_LAUNCH(u16, 4);
-      else TD_WGB_LAUNCH(float, 4);
-    } else {
-      if (dtype == TD_BF16) TD_WGB_LAUNCH(u16, 2);
-      else TD_WGB_LAUNCH(float, 2);
-    }
+    if (pw == 2) conv_wgrad_wide_batch_kernel<<<grid, 1024, 0, st>>>(dev, xi);
+    else if (dtype == TD_BF16) TD_WGB_LAUNCH(u16);
+    else TD_WGB_LAUNCH(float);
 #undef TD_WGB_LAUNCH
     rc = check_launch("td_conv_wgrad_batch");
     if (rc) return rc;
