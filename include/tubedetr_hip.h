@@ -514,6 +514,60 @@ typedef struct td_resample_job {
 size_t td_clip_resample_table_bytes(int n_jobs);
 int td_clip_resample(const td_resample_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
 
+/* td_clip_resample with the decoder's native frames as the source (an addition WITHIN ABI 11: nothing above changed, and
+ * td_abi_version() stays 11).  A job is a td_resample_job plus the source format; with fmt = TD_SRC_RGB24 it IS that job
+ * (plane0 / pitch0 / frame_stride = src / src_pitch / src_frame_stride), so one launch may mix formats.
+ *   TD_SRC_I420 (ffmpeg yuv420p; yuvj420p with full_range = 1): per frame a Y plane of sh x sw bytes, then U, then V,
+ *        each ch x cw with ch = (sh + 1) / 2, cw = (sw + 1) / 2 (integer division);
+ *   TD_SRC_NV12: the Y plane, then one plane of ch rows of cw interleaved (U, V) byte pairs (plane1; plane2 unused).
+ * Every plane has its own pointer (of frame 0) and row pitch; frame t of each plane lies t * frame_stride bytes further.
+ * An ffmpeg rawvideo pipe packs tightly: pitches sw, cw, cw (NV12: sw, 2 cw), plane1 = plane0 + sw sh,
+ * plane2 = plane1 + cw ch, frame_stride = sw sh + 2 cw ch.  Odd sw, sh are legal: the last column / row shares its
+ * chroma sample.  No byte outside a plane's rows of the job's T frames is read.
+ * Conversion rule (exact integers, so results are reproducible to the bit): source pixel (y, x) uses chroma sample
+ * (y >> 1, x >> 1) - replication, no interpolation - and, in int32, with yo = 16 (limited range) or 0 (full range),
+ *   c = Y - yo, d = U - 128, e = V - 128,
+ *   R = clamp((cy c + crv e + 32768) >> 16), G = clamp((cy c - cgu d - cgv e + 32768) >> 16),
+ *   B = clamp((cy c + cbu d + 32768) >> 16)          (>> arithmetic = floor division; clamp to [0, 255]).
+ * Coefficients are round(65536 x) of the textbook values; from Kr, Kb, Kg = 1 - Kr - Kb: crv = 2 (1 - Kr) s,
+ * cbu = 2 (1 - Kb) s, cgu = 2 Kb (1 - Kb) / Kg s, cgv = 2 Kr (1 - Kr) / Kg s, with cy = 255 / 219, s = 255 / 224 for
+ * limited range and cy = s = 1 for full range:
+ *                      cy      crv     cbu     cgu    cgv
+ *   BT.601 limited   76309  104597  132201   25675  53279
+ *   BT.601 full      65536   91881  116130   22553  46802
+ *   BT.709 limited   76309  117489  138438   13975  34925
+ *   BT.709 full      65536  103206  121609   12276  30679
+ * (within 0.502 of a level of the float64 formula over all (Y, U, V); |accumulator| < 3.6e7).  The job's output is, byte
+ * for byte, what td_clip_resample produces from the rgb24 frames this rule makes of the source: flip reads converted
+ * column sw - 1 - j; sampling rule, window, destinations, mask, zero fill and limits are td_clip_resample's.  Agreement
+ * with any decoder library's own yuv -> rgb conversion (ffmpeg's swscale) is not claimed.  The job table is sized by
+ * td_clip_resample_src_table_bytes (its records are larger than td_clip_resample's). */
+#define TD_SRC_RGB24 0
+#define TD_SRC_I420 1
+#define TD_SRC_NV12 2
+#define TD_MATRIX_BT601 0
+#define TD_MATRIX_BT709 1
+typedef struct td_resample_src_job {
+  const void* plane0; /* rgb24 pixels, or Y */
+  const void* plane1; /* I420: U; NV12: UV pairs; RGB24: ignored */
+  const void* plane2; /* I420: V; else ignored */
+  long long frame_stride;
+  int pitch0, pitch1, pitch2;
+  int fmt;
+  int matrix, full_range; /* I420 / NV12 only */
+  int T, sh, sw;
+  int flip;
+  int rh, rw;
+  int wy, wx, wh, ww;
+  void* dst;
+  int planar;
+  int frame_off;
+  int H, W;
+  void* mask;
+} td_resample_src_job;
+size_t td_clip_resample_src_table_bytes(int n_jobs);
+int td_clip_resample_src(const td_resample_src_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,11 @@
-"""Time the device-side clip augmentation (td_clip_resample) for one training batch: 16 clips of 100 decoded frames.
+"""Time the device-side clip augmentation (td_clip_resample / td_clip_resample_src) for one training batch: 16 clips of
+100 decoded frames.
 
 Scenarios: (a) final 352 x 352 (what bench.py feeds) from 360 x 360 and 720 x 720 sources, (b) final 330 x 586 from
 360 x 640 and 1280 x 720 sources (16:9 video at resolution 352); each with the evaluation plan (one resize) and with the
-training transform's second arm (resize, crop, second resize: two launches through a uint8 intermediate).
+training transform's second arm (resize, crop, second resize: two launches through a uint8 intermediate).  Every
+scenario runs twice in the same process, with the same plans: the source as packed rgb24 (3 bytes per pixel) and as
+yuv420p (I420, 1.5 bytes per pixel, converted by the launch that reads it); ``pairs`` in the output puts the two side by side.
 
 Per scenario:
   device_ms_per_batch      device events around >= 200 ms of repeated launches of the whole batch, after warm-up
@@ -29,7 +32,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from tubedetr_amd import _hip  # noqa: E402
-from tubedetr_amd.augment import make_video_transforms, resample_job  # noqa: E402
+from tubedetr_amd.augment import make_video_transforms, resample_job, resample_src_job  # noqa: E402
 
 HBM_PEAK = 8.0e12
 
@@ -39,10 +42,12 @@ def first_tap(v, n_src, n_dst):
     return num // (2 * n_dst) if num > 0 else 0
 
 
-def source_bytes(T, sh, sw, st):
+def source_bytes(T, sh, sw, st, pix_fmt="rgb24"):
     rows = min(first_tap(st.wy + st.wh - 1, sh, st.rh) + 1, sh - 1) - first_tap(st.wy, sh, st.rh) + 1
     cols = min(first_tap(st.wx + st.ww - 1, sw, st.rw) + 1, sw - 1) - first_tap(st.wx, sw, st.rw) + 1
-    return T * rows * cols * 3
+    if pix_fmt == "rgb24":
+        return T * rows * cols * 3
+    return T * (rows * cols + 2 * ((rows + 1) // 2) * ((cols + 1) // 2))  # the window's Y samples + their share of the two chroma planes
 
 
 def plans_for(kind, n, T, h, w):
@@ -83,30 +88,35 @@ def cv2_host_ms(T, h, w, plan):
     return round(1e3 * (time.perf_counter() - t0), 2)
 
 
-def scenario(name, kind, h, w, n_clips, T, dev, min_ms):
+def scenario(name, kind, h, w, n_clips, T, dev, min_ms, pix_fmt, plans, plan_ms):
     lib = _hip.lib()
-    plans, plan_ms = plans_for(kind, n_clips, T, h, w)
+    yuv = pix_fmt != "rgb24"
     H, W = max(p.hw[0] for p in plans), max(p.hw[1] for p in plans)
-    clip_bytes = T * h * w * 3
+    clip_bytes = T * (h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)) if yuv else T * h * w * 3
     # decoded frames: random pixels made on the device (the timed launches do not care where they came from)
     raw = torch.randint(0, 256, (n_clips, clip_bytes), dtype=torch.uint8, device=dev)
     video = torch.empty((n_clips * T, 3, H, W), dtype=torch.uint8, device=dev)
     mask = torch.empty((n_clips * T, H, W), dtype=torch.bool, device=dev)
     first, final, mids, abytes = [], [], [], 0
+    src_first, src_final = yuv, yuv and len(plans[0].stages) == 1  # the launch that reads the decoded frames takes their format
+
+    def job(use_src, fmt, *a, **kw):
+        return resample_src_job(*a, fmt, **kw) if use_src else resample_job(*a, **kw)
+
     for i, p in enumerate(plans):
-        src, sh, sw, flip = raw[i].data_ptr(), h, w, p.flip
+        src, sh, sw, flip, fmt = raw[i].data_ptr(), h, w, p.flip, pix_fmt
         if len(p.stages) == 2:
             s = p.stages[0]
             mid = torch.empty((T, s.wh, s.ww, 3), dtype=torch.uint8, device=dev)
             mids.append(mid)
-            first.append(resample_job(src, T, sh, sw, flip, s, mid.data_ptr()))
-            abytes += source_bytes(T, sh, sw, s) + mid.numel()
-            src, sh, sw, flip = mid.data_ptr(), s.wh, s.ww, False
+            first.append(job(src_first, fmt, src, T, sh, sw, flip, s, mid.data_ptr()))
+            abytes += source_bytes(T, sh, sw, s, fmt) + mid.numel()
+            src, sh, sw, flip, fmt = mid.data_ptr(), s.wh, s.ww, False, "rgb24"
         s = p.stages[-1]
-        final.append(resample_job(src, T, sh, sw, flip, s, video.data_ptr(), planar=True, frame_off=i * T, H=H, W=W, mask=mask.data_ptr()))
-        abytes += source_bytes(T, sh, sw, s) + T * 4 * H * W
-    launches = [(_hip.ResampleJob * len(j))(*j) for j in (first, final) if j]
-    nb = int(lib.td_clip_resample_table_bytes(n_clips))
+        final.append(job(src_final, fmt, src, T, sh, sw, flip, s, video.data_ptr(), planar=True, frame_off=i * T, H=H, W=W, mask=mask.data_ptr()))
+        abytes += source_bytes(T, sh, sw, s, fmt) + T * 4 * H * W
+    launches = [((_hip.ResampleSrcJob if use_src else _hip.ResampleJob) * len(j))(*j) for j, use_src in ((first, src_first), (final, src_final)) if j]
+    nb = int(max(lib.td_clip_resample_table_bytes(n_clips), lib.td_clip_resample_src_table_bytes(n_clips)))
     ring = 64  # job-table pairs: a pair is rewritten only after `ring` later launches, each synchronised batch-wise below
     tab_h = torch.empty(ring * nb, dtype=torch.uint8, pin_memory=True)
     tab_d = torch.empty(ring * nb, dtype=torch.uint8, device=dev)
@@ -116,7 +126,8 @@ def scenario(name, kind, h, w, n_clips, T, dev, min_ms):
         for arr in launches:
             o = (slot[0] % ring) * nb
             slot[0] += 1
-            _hip.check(lib.td_clip_resample(arr, len(arr), tab_h.data_ptr() + o, tab_d.data_ptr() + o, nb, _hip.stream_ptr()), "td_clip_resample")
+            fn = lib.td_clip_resample_src if isinstance(arr[0], _hip.ResampleSrcJob) else lib.td_clip_resample
+            _hip.check(fn(arr, len(arr), tab_h.data_ptr() + o, tab_d.data_ptr() + o, nb, _hip.stream_ptr()), "td_clip_resample")
 
     def timed(reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -154,13 +165,13 @@ def scenario(name, kind, h, w, n_clips, T, dev, min_ms):
     torch.cuda.synchronize()
     h2d_ms = e0.elapsed_time(e1) / 4
     return {
-        "name": name, "plan": kind, "source_hw": [h, w], "final_hw_max": [H, W], "clips": n_clips, "frames_per_clip": T, "launches_per_batch": len(launches),
+        "name": name, "plan": kind, "pix_fmt": pix_fmt, "source_hw": [h, w], "final_hw_max": [H, W], "clips": n_clips, "frames_per_clip": T, "launches_per_batch": len(launches),
         "device_ms_per_batch": round(ms, 4), "timed_batches": done, "timed_device_ms": round(total, 1),
         "algorithmic_bytes": int(abytes), "achieved_GBps": round(abytes / (ms * 1e-3) / 1e9, 1), "share_of_hbm_peak": round(abytes / (ms * 1e-3) / HBM_PEAK, 4),
         "host_plan_ms_per_clip": round(plan_ms, 3), "host_pack_ms_per_clip": round(1e3 * float(np.median(pack)), 2),
         "h2d_bytes_per_clip": clip_bytes, "h2d_ms_per_clip": round(h2d_ms, 3), "h2d_GBps": round(clip_bytes / (h2d_ms * 1e-3) / 1e9, 1),
         "h2d_ms_per_batch": round(h2d_ms * n_clips, 2),
-        "cv2_host_ms_per_clip": cv2_host_ms(T, h, w, plans[0]),
+        "cv2_host_ms_per_clip": cv2_host_ms(T, h, w, plans[0]) if not yuv else "not measured",
     }
 
 
@@ -179,16 +190,21 @@ def main():
         step_ms = json.load(open(os.path.join(ROOT, "BENCH_r06.json")))["parsed"]["ms_per_step"]
     except Exception:  # noqa: BLE001
         pass
-    rows = []
+    rows, pairs = [], []
+    paired = ("h2d_bytes_per_clip", "h2d_ms_per_batch", "host_pack_ms_per_clip", "device_ms_per_batch")
     for name, h, w in (("352x352 from 360x360", 360, 360), ("352x352 from 720x720", 720, 720), ("330x586 from 360x640", 360, 640), ("330x586 from 720x1280", 720, 1280)):
         for kind in ("eval", "train-branch-2"):
-            rows.append(scenario(name, kind, h, w, a.clips, a.frames, dev, a.min_ms))
-            r = rows[-1]
-            print(f"{name:24s} {kind:15s} {r['device_ms_per_batch']:8.3f} ms/batch  {r['achieved_GBps']:7.1f} GB/s ({100 * r['share_of_hbm_peak']:.1f} % of 8 TB/s)  "
-                  f"H2D {r['h2d_ms_per_batch']:.1f} ms/batch at {r['h2d_GBps']} GB/s  plan {r['host_plan_ms_per_clip']} ms  pack {r['host_pack_ms_per_clip']} ms/clip  "
-                  f"cv2 {r['cv2_host_ms_per_clip']}", flush=True)
+            plans, plan_ms = plans_for(kind, a.clips, a.frames, h, w)
+            for pix_fmt in ("rgb24", "yuv420p"):  # the twin: same plans, same process, source in I420
+                rows.append(scenario(name, kind, h, w, a.clips, a.frames, dev, a.min_ms, pix_fmt, plans, plan_ms))
+                r = rows[-1]
+                if pix_fmt == "yuv420p":
+                    pairs.append({"name": name, "plan": kind, "rgb24": {k: rows[-2][k] for k in paired}, "yuv420p": {k: r[k] for k in paired}})
+                print(f"{name:24s} {kind:15s} {pix_fmt:8s} {r['device_ms_per_batch']:8.3f} ms/batch  {r['achieved_GBps']:7.1f} GB/s ({100 * r['share_of_hbm_peak']:.1f} % of 8 TB/s)  "
+                      f"H2D {r['h2d_ms_per_batch']:.1f} ms/batch at {r['h2d_GBps']} GB/s  plan {r['host_plan_ms_per_clip']} ms  pack {r['host_pack_ms_per_clip']} ms/clip  "
+                      f"cv2 {r['cv2_host_ms_per_clip']}", flush=True)
     out = {"device": torch.cuda.get_device_name(0), "hbm_peak_Bps": HBM_PEAK, "step_ms_of_the_16_clip_training_step": step_ms,
-           "step_ms_source": "BENCH_r06.json (bench.py --gpus 1 --steps 20 --warmup 5)", "scenarios": rows}
+           "step_ms_source": "BENCH_r06.json (bench.py --gpus 1 --steps 20 --warmup 5)", "scenarios": rows, "pairs": pairs}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)

@@ -56,6 +56,17 @@ class ResampleJob(C.Structure):
                [("dst", C.c_void_p)] + [(n, C.c_int) for n in ("planar", "frame_off", "H", "W")] + [("mask", C.c_void_p)]
 
 
+TD_SRC_RGB24, TD_SRC_I420, TD_SRC_NV12 = 0, 1, 2
+TD_MATRIX_BT601, TD_MATRIX_BT709 = 0, 1
+
+
+class ResampleSrcJob(C.Structure):
+    """td_resample_src_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("plane0", "plane1", "plane2")] + [("frame_stride", C.c_longlong)] + \
+               [(n, C.c_int) for n in ("pitch0", "pitch1", "pitch2", "fmt", "matrix", "full_range", "T", "sh", "sw", "flip", "rh", "rw", "wy", "wx", "wh", "ww")] + \
+               [("dst", C.c_void_p)] + [(n, C.c_int) for n in ("planar", "frame_off", "H", "W")] + [("mask", C.c_void_p)]
+
+
 class Epilogue(C.Structure):
     _fields_ = [
         ("bias", C.c_void_p),
@@ -127,12 +138,14 @@ _SIGS = {
     "td_mha_lean_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _U32, _P, _I, _P],
     "td_mha_lean_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _U32, _P, _I, _P],
     "td_clip_resample": [C.POINTER(ResampleJob), _I, _P, _P, _SZ, _P],
+    "td_clip_resample_src": [C.POINTER(ResampleSrcJob), _I, _P, _P, _SZ, _P],
 }
 _SIZE_SIGS = {
     "td_grad_norm_ws_bytes": [],
     "td_mha_lean_stats_bytes": [_I, _I, _I],
     "td_conv_wgrad_batch_table_bytes": [_I],
     "td_clip_resample_table_bytes": [_I],
+    "td_clip_resample_src_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],

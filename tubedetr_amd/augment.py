@@ -5,7 +5,8 @@ datasets/video_transforms.py:327-443: random horizontal flip, random resize, ran
 bookkeeping, caption left/right swap; at evaluation one resize).  Here the host only DRAWS: ``plan`` consumes Python's
 ``random`` and torch's generator in the reference's order, does the box arithmetic in the reference's fp32 operations,
 and returns a small record that says which resamples the device has to run; ``ClipPipeline.stage_raw``
-(tubedetr_amd/data.py) sends the decoded frames once, as they came out of the decoder, and enqueues those launches.
+(tubedetr_amd/data.py) sends the decoded frames once, as they came out of the decoder - rgb24 arrays, or yuv420p / nv12
+buffers described by a ``DecodedClip``, half the bytes - and enqueues those launches.
 """
 from __future__ import annotations
 
@@ -186,6 +187,101 @@ def resample_job(src: int, T: int, sh: int, sw: int, flip: bool, stage: Resample
     j.rh, j.rw, j.wy, j.wx, j.wh, j.ww = stage.rh, stage.rw, stage.wy, stage.wx, stage.wh, stage.ww
     j.dst, j.planar, j.frame_off, j.H, j.W, j.mask = dst, int(bool(planar)), frame_off, H, W, mask
     return j
+
+
+_PIX_FMTS = ("rgb24", "yuv420p", "nv12")
+_MATRICES = ("bt601", "bt709")
+
+
+@dataclass
+class DecodedClip:
+    """T decoded frames of h x w as they came off the decoder's pipe: ``data`` is the flat uint8 buffer, tightly packed
+    (ffmpeg ``-f rawvideo -pix_fmt <pix_fmt>``).  yuv420p: per frame the Y plane, then U, then V ((h + 1) // 2 rows of
+    (w + 1) // 2 bytes each); nv12: the Y plane, then the interleaved UV plane; rgb24: (h, w, 3).  ``matrix`` and
+    ``full_range`` say how yuv becomes rgb (include/tubedetr_hip.h; yuvj420p is yuv420p with ``full_range=True``)."""
+    data: object
+    T: int
+    h: int
+    w: int
+    pix_fmt: str = "yuv420p"
+    matrix: str = "bt601"
+    full_range: bool = False
+
+    def __post_init__(self):
+        if self.pix_fmt not in _PIX_FMTS:
+            raise ValueError(f"pix_fmt {self.pix_fmt!r}: one of {_PIX_FMTS}")
+        if self.matrix not in _MATRICES:
+            raise ValueError(f"matrix {self.matrix!r}: one of {_MATRICES}")
+        self.T, self.h, self.w = int(self.T), int(self.h), int(self.w)
+        d = torch.as_tensor(self.data)
+        if d.dtype != torch.uint8 or d.is_cuda:
+            raise ValueError("data is a uint8 buffer on the host")
+        d = d.contiguous().view(-1)
+        if d.numel() != self.T * self.nbytes_per_frame:
+            raise ValueError(f"{d.numel()} bytes for {self.T} {self.pix_fmt} frames of {self.h} x {self.w} ({self.nbytes_per_frame} bytes each)")
+        self.data = d
+
+    @property
+    def chroma_hw(self) -> Tuple[int, int]:
+        return (self.h + 1) // 2, (self.w + 1) // 2
+
+    @property
+    def nbytes_per_frame(self) -> int:
+        if self.pix_fmt == "rgb24":
+            return 3 * self.w * self.h
+        ch, cw = self.chroma_hw
+        return self.w * self.h + 2 * cw * ch
+
+    @property
+    def nbytes(self) -> int:
+        return self.T * self.nbytes_per_frame
+
+
+def resample_src_job(src: int, T: int, sh: int, sw: int, flip: bool, stage: ResampleStage, dst: int, pix_fmt: str = "rgb24", matrix: str = "bt601",
+                     full_range: bool = False, planar: bool = False, frame_off: int = 0, H: int = 0, W: int = 0, mask: Optional[int] = None,
+                     planes: Optional[Sequence[int]] = None, pitches: Optional[Sequence[int]] = None, frame_stride: Optional[int] = None):
+    """One ``td_resample_src_job``: ``resample_job`` for T frames in ``pix_fmt`` at device address ``src``.  Without
+    ``planes`` / ``pitches`` / ``frame_stride`` the frames are tightly packed (``DecodedClip``); else ``planes`` are the
+    device addresses of frame 0's planes (``src`` is ignored) and ``pitches`` their row pitches."""
+    from . import _hip
+
+    ch, cw = (sh + 1) // 2, (sw + 1) // 2
+    if pix_fmt == "rgb24":
+        fmt, tight, sizes = _hip.TD_SRC_RGB24, [3 * sw], [3 * sw * sh]
+    elif pix_fmt == "yuv420p":
+        fmt, tight, sizes = _hip.TD_SRC_I420, [sw, cw, cw], [sw * sh, cw * ch, cw * ch]
+    elif pix_fmt == "nv12":
+        fmt, tight, sizes = _hip.TD_SRC_NV12, [sw, 2 * cw], [sw * sh, 2 * cw * ch]
+    else:
+        raise ValueError(f"pix_fmt {pix_fmt!r}: one of {_PIX_FMTS}")
+    pitches = list(tight if pitches is None else pitches)
+    if planes is None:
+        planes = [src + sum(sizes[:i]) for i in range(len(sizes))]
+        if frame_stride is None:
+            frame_stride = sum(sizes)
+    assert len(planes) == len(pitches) == len(sizes) and frame_stride is not None, "one address and one pitch per plane, and the frame stride"
+    planes, pitches = list(planes) + [None] * (3 - len(sizes)), pitches + [0] * (3 - len(sizes))
+    j = _hip.ResampleSrcJob()
+    j.plane0, j.plane1, j.plane2 = planes
+    j.pitch0, j.pitch1, j.pitch2 = pitches
+    j.frame_stride, j.fmt, j.matrix, j.full_range = frame_stride, fmt, _MATRICES.index(matrix), int(bool(full_range))
+    j.T, j.sh, j.sw, j.flip = T, sh, sw, int(bool(flip))
+    j.rh, j.rw, j.wy, j.wx, j.wh, j.ww = stage.rh, stage.rw, stage.wy, stage.wx, stage.wh, stage.ww
+    j.dst, j.planar, j.frame_off, j.H, j.W, j.mask = dst, int(bool(planar)), frame_off, H, W, mask
+    return j
+
+
+def clip_resample_src(jobs: Sequence, device) -> tuple:
+    """``clip_resample`` for ``resample_src_job`` jobs (td_clip_resample_src)."""
+    from . import _hip
+
+    lib = _hip.lib()
+    nb = int(lib.td_clip_resample_src_table_bytes(len(jobs)))
+    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
+    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
+    arr = (_hip.ResampleSrcJob * len(jobs))(*jobs)
+    _hip.check(lib.td_clip_resample_src(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_clip_resample_src")
+    return host, dev
 
 
 def clip_resample(jobs: Sequence, device) -> tuple:

@@ -13,7 +13,16 @@
 //   * the band is ONE contiguous byte range of every destination plane (full-width rows), so a lane produces the four
 //     bytes of an ALIGNED destination dword whatever W is, finds each byte's row by compares and stores 4 bytes; only a
 //     band's first / last partial dword falls back to byte stores (its other bytes belong to the neighbour band).
+//
+// td_clip_resample_src adds the source format (I420 / NV12 beside rgb24): the same kernel, instantiated on a job record that
+// carries the planes.  Only the staging step differs: a lane takes the 4 pixels of one ALIGNED Y dword and their 2 or 3
+// chroma samples (aligned dwords again, funnel-shifted to the sample), converts them by the header's integer rule and
+// writes the 12 rgb bytes into the slot - so the slots hold what the rgb24 staging would have put there from the
+// converted frame, and the tables and the producing half are shared: bit equality with the rgb24 path by construction.
+// Every plane has its own extent guard.  The 3 dword stores of a lane go to dwords 3d, 3d + 1, 3d + 2: a stride of 3
+// dwords over the lanes, coprime with the 32 banks of a store, so each of the three is conflict-free.
 #include <algorithm>
+#include <type_traits>
 
 #include "td_common.h"
 
@@ -22,6 +31,7 @@ namespace td {
 constexpr int kThreads = 256;
 constexpr int kMaxBand = 4;        // output rows per workgroup
 constexpr int kStageDepth = 4;     // staged dwords per lane and source row held in registers (rows of up to 1365 pixels take the fast path)
+constexpr int kYuvDepth = 2;       // the same for Y dwords of an I420 / NV12 row (rows of up to 2045 pixels): a staged Y dword brings up to 4 chroma dwords along
 constexpr int kFrameChunk = 4;     // frames per workgroup (amortises the column table)
 constexpr int kMaxSide = 16384;    // (2x + 1) * sw stays below 2^30
 constexpr int kMaxSrcCols = 8192;  // 3 * (column - cmin) fits the table's 16-bit offsets
@@ -38,6 +48,18 @@ struct ResampleParams {
   int cmin;                     // first (flipped) source column any output column of the window reads
   int slot_bytes;               // LDS bytes of one staged source row
   int R, nbands, block_begin;
+};
+
+// td_clip_resample_src: the job record + the source format.  RGB24: the base describes the job, as in td_clip_resample.
+// I420 / NV12: src / pitch / src_bytes are the Y plane's; a slot holds 12 bytes per staged Y dword.
+struct SrcParams : ResampleParams {
+  const unsigned char* plane1;  // U (I420), interleaved UV (NV12)
+  const unsigned char* plane2;  // V (I420)
+  long long bytes1, bytes2;     // extents of the job's chroma planes from plane1 / plane2
+  int pitch1, pitch2;
+  int fmt;
+  int nd;                       // staged Y dwords of one source row
+  int yo, cy, crv, cgu, cgv, cbu;
 };
 
 // the table's pointers are loaded from memory, so the compiler cannot see that they are global: say so (global_load / global_store
@@ -69,7 +91,144 @@ __device__ __forceinline__ uint32_t load_dword_guarded(const unsigned char* a, c
   return v;
 }
 
-__global__ __launch_bounds__(kThreads) void clip_resample_kernel(const ResampleParams* __restrict__ tab, int n_jobs) {
+// clamp(acc >> 16) to [0, 255], written as a clamp of the accumulator BEFORE the shift (the same integer for every acc).
+// The shift-then-clamp form is selected as v_ashr_pk_u8_i32 for pairs of channels, and the bytes packed next to its result
+// came back ORed with the unclamped second value on the MI355X (hipcc roc-7.2.0): do not "simplify" this back.
+__device__ __forceinline__ uint32_t shift_clamp_u8(int acc) { return (uint32_t)min(max(acc, 0), 0xffffff) >> 16; }
+
+// 4 bytes from the unaligned address a + (sh >> 3) of the aligned dword pair (lo at a, hi at a + 4)
+__device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, int sh) { return (uint32_t)((((unsigned long long)hi << 32) | lo) >> sh); }
+
+// where the staged Y dword d of source row srow and its chroma samples live: y is dword-aligned and holds columns x0 .. x0 + 3
+// (x0 may start before column 0 or end past the row: those pixels are converted from whatever the guards let through and never
+// read); c1 / c2 are the addresses of chroma sample x0 >> 1 (NV12: c1 is its (U, V) pair)
+struct YuvAddr { const unsigned char *y, *c1, *c2; int x0, o; };
+__device__ __forceinline__ YuvAddr yuv_addr(const SrcParams& p, int t, int srow, int d) {
+  const long long f = (long long)t * p.src_frame_stride;
+  const unsigned char* rp = p.src + f + (long long)srow * p.pitch + p.cmin;
+  YuvAddr a;
+  a.o = (int)((uintptr_t)rp & 3);
+  a.y = rp - a.o + 4 * d;
+  a.x0 = p.cmin - a.o + 4 * d;
+  const int cx = a.x0 >> 1, crow = srow >> 1;
+  if (p.fmt == TD_SRC_NV12) {
+    a.c1 = p.plane1 + f + (long long)crow * p.pitch1 + 2 * cx;
+    a.c2 = nullptr;
+  } else {
+    a.c1 = p.plane1 + f + (long long)crow * p.pitch1 + cx;
+    a.c2 = p.plane2 + f + (long long)crow * p.pitch2 + cx;
+  }
+  return a;
+}
+
+// the aligned dwords that hold a Y dword's chroma: I420 c[0..1] = U, c[2..3] = V (3 samples from any alignment span at most 2 dwords),
+// NV12 c[0..2] (3 pairs span at most 3)
+__device__ __forceinline__ void load_yuv(const SrcParams& p, const YuvAddr& a, uint32_t& y, uint32_t c[4]) {
+  y = load_dword_guarded(a.y, p.src, p.src + p.src_bytes);
+  const unsigned char* b1 = a.c1 - ((uintptr_t)a.c1 & 3);
+  c[0] = load_dword_guarded(b1, p.plane1, p.plane1 + p.bytes1);
+  c[1] = load_dword_guarded(b1 + 4, p.plane1, p.plane1 + p.bytes1);
+  if (p.fmt == TD_SRC_NV12) {
+    c[2] = load_dword_guarded(b1 + 8, p.plane1, p.plane1 + p.bytes1);
+    c[3] = 0;
+  } else {
+    const unsigned char* b2 = a.c2 - ((uintptr_t)a.c2 & 3);
+    c[2] = load_dword_guarded(b2, p.plane2, p.plane2 + p.bytes2);
+    c[3] = load_dword_guarded(b2 + 4, p.plane2, p.plane2 + p.bytes2);
+  }
+}
+
+// the header's integer rule on the 4 pixels of a Y dword -> their 12 rgb bytes.  The accumulators are the header's, term by term
+// regrouped (exact in int32): cy (Y - yo) + crv (V - 128) + 32768 = cy Y + (crv V + bias_r), the bracket once per chroma sample.
+// Every factor is below 2^24: 24-bit multiplies (full rate; the 32-bit ones are not).
+__device__ __forceinline__ void yuv_to_rgb4(const SrcParams& p, const YuvAddr& a, uint32_t y, const uint32_t c[4], uint32_t out[3]) {
+  uint32_t u, v;  // byte i = sample (x0 >> 1) + i
+  if (p.fmt == TD_SRC_NV12) {
+    const int sh = 8 * (int)((uintptr_t)a.c1 & 3);
+    const uint32_t w0 = funnel(c[0], c[1], sh), w1 = funnel(c[1], c[2], sh);  // U0 V0 U1 V1 | U2 V2 . .
+    u = (w0 & 0xff) | ((w0 >> 8) & 0xff00) | ((w1 & 0xff) << 16);
+    v = ((w0 >> 8) & 0xff) | ((w0 >> 16) & 0xff00) | ((w1 & 0xff00) << 8);
+  } else {
+    u = funnel(c[0], c[1], 8 * (int)((uintptr_t)a.c1 & 3));
+    v = funnel(c[2], c[3], 8 * (int)((uintptr_t)a.c2 & 3));
+  }
+  const int base = 32768 - p.cy * p.yo;  // uniform: scalar arithmetic
+  const int bias_r = base - 128 * p.crv, bias_g = base + 128 * (p.cgu + p.cgv), bias_b = base - 128 * p.cbu;
+  int cr[3], cg[3], cb[3];  // the chroma part of the three accumulators, per chroma sample
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const int uu = (int)((u >> (8 * i)) & 0xff), vv = (int)((v >> (8 * i)) & 0xff);
+    cr[i] = __mul24(p.crv, vv) + bias_r;
+    cg[i] = bias_g - __mul24(p.cgu, uu) - __mul24(p.cgv, vv);
+    cb[i] = __mul24(p.cbu, uu) + bias_b;
+  }
+  const bool odd = a.x0 & 1;  // column x0 + j uses sample (x0 + j) >> 1 = (x0 >> 1) + ((j + odd) >> 1): 0, 0 | 1, 1, 1 | 2
+  out[0] = out[1] = out[2] = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int yy = __mul24(p.cy, (int)((y >> (8 * j)) & 0xff));
+    int r, g, b;
+    if (j == 0 || j == 2) { r = cr[j >> 1]; g = cg[j >> 1]; b = cb[j >> 1]; }
+    else { r = odd ? cr[(j + 1) >> 1] : cr[j >> 1]; g = odd ? cg[(j + 1) >> 1] : cg[j >> 1]; b = odd ? cb[(j + 1) >> 1] : cb[j >> 1]; }
+    const uint32_t px[3] = {shift_clamp_u8(yy + r), shift_clamp_u8(yy + g), shift_clamp_u8(yy + b)};
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) out[(3 * j + ch) >> 2] |= px[ch] << (8 * ((3 * j + ch) & 3));
+  }
+}
+
+// staging of an I420 / NV12 band: as the rgb24 staging below, with the conversion between the loads and the LDS writes
+__device__ __forceinline__ void stage_yuv(const SrcParams& p, const RowEntry* row, int* slot_off, unsigned char* slots, int t, int n_live, int tid) {
+  const int nd = p.nd;
+  if (nd <= kYuvDepth * kThreads) {
+    uint32_t y[2 * kMaxBand][kYuvDepth], c[2 * kMaxBand][kYuvDepth][4];
+#pragma unroll
+    for (int s = 0; s < 2 * kMaxBand; s++) {
+      if (s < 2 * n_live) {
+        const int srow = (s & 1) ? row[s >> 1].y1 : row[s >> 1].y0;
+#pragma unroll
+        for (int k = 0; k < kYuvDepth; k++) {
+          const int d = tid + k * kThreads;
+          if (d < nd) load_yuv(p, yuv_addr(p, t, srow, d), y[s][k], c[s][k]);
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 2 * kMaxBand; s++) {
+      if (s < 2 * n_live) {
+        const int srow = (s & 1) ? row[s >> 1].y1 : row[s >> 1].y0;
+        uint32_t* dst_lds = (uint32_t*)(slots + (size_t)s * p.slot_bytes);
+#pragma unroll
+        for (int k = 0; k < kYuvDepth; k++) {
+          const int d = tid + k * kThreads;
+          if (d < nd) {
+            const YuvAddr a = yuv_addr(p, t, srow, d);
+            uint32_t out[3];
+            yuv_to_rgb4(p, a, y[s][k], c[s][k], out);
+            dst_lds[3 * d] = out[0]; dst_lds[3 * d + 1] = out[1]; dst_lds[3 * d + 2] = out[2];
+            if (d == 0) slot_off[s] = 3 * a.o;
+          }
+        }
+      }
+    }
+  } else {
+    for (int s = 0; s < 2 * n_live; s++) {
+      const int srow = (s & 1) ? row[s >> 1].y1 : row[s >> 1].y0;
+      uint32_t* dst_lds = (uint32_t*)(slots + (size_t)s * p.slot_bytes);
+      for (int d = tid; d < nd; d += kThreads) {
+        const YuvAddr a = yuv_addr(p, t, srow, d);
+        uint32_t y, c[4], out[3];
+        load_yuv(p, a, y, c);
+        yuv_to_rgb4(p, a, y, c, out);
+        dst_lds[3 * d] = out[0]; dst_lds[3 * d + 1] = out[1]; dst_lds[3 * d + 2] = out[2];
+        if (d == 0) slot_off[s] = 3 * a.o;
+      }
+    }
+  }
+}
+
+// P = ResampleParams: rgb24 sources only (td_clip_resample); P = SrcParams: the job says (td_clip_resample_src)
+template <typename P>
+__global__ __launch_bounds__(kThreads) void clip_resample_kernel(const P* __restrict__ tab, int n_jobs) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, b = blockIdx.x;
   int lo = 0, hi = n_jobs - 1;
@@ -77,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void clip_resample_kernel(const ResampleP
     const int mid = (lo + hi + 1) >> 1;
     if (tab[mid].block_begin <= b) lo = mid; else hi = mid - 1;
   }
-  const ResampleParams p = tab[lo];
+  const P p = tab[lo];
   const int local = b - p.block_begin;
   const int band = local % p.nbands, chunk = local / p.nbands;
   const int yb = band * p.R;
@@ -112,7 +271,11 @@ __global__ __launch_bounds__(kThreads) void clip_resample_kernel(const ResampleP
     const unsigned char* fsrc = p.src + (long long)t * p.src_frame_stride;
     // ---- stage the band's source rows
     const int nd = p.slot_bytes >> 2;
-    if (nd <= kStageDepth * kThreads) {
+    bool yuv = false;
+    if constexpr (std::is_same<P, SrcParams>::value) yuv = p.fmt != TD_SRC_RGB24;
+    if (yuv) {
+      if constexpr (std::is_same<P, SrcParams>::value) stage_yuv(p, row, slot_off, slots, t, n_live, tid);
+    } else if (nd <= kStageDepth * kThreads) {
       // all loads of the band in flight together (a load-then-LDS-write loop would pay one memory latency per source row)
       uint32_t v[2 * kMaxBand][kStageDepth];
 #pragma unroll
@@ -203,42 +366,95 @@ __global__ __launch_bounds__(kThreads) void clip_resample_kernel(const ResampleP
   }
 }
 
-static size_t table_bytes(int n_jobs) { return (((size_t)n_jobs * sizeof(ResampleParams)) + 255) & ~(size_t)255; }
+template <typename P>
+static size_t table_bytes(int n_jobs) { return (((size_t)n_jobs * sizeof(P)) + 255) & ~(size_t)255; }
 
-}  // namespace td
+// round(65536 x) of the textbook values (include/tubedetr_hip.h): [matrix][full_range] = {yo, cy, crv, cgu, cgv, cbu}
+static const int kYuvCoef[2][2][6] = {
+    {{16, 76309, 104597, 25675, 53279, 132201}, {0, 65536, 91881, 22553, 46802, 116130}},   // BT.601
+    {{16, 76309, 117489, 13975, 34925, 138438}, {0, 65536, 103206, 12276, 30679, 121609}},  // BT.709
+};
 
-using namespace td;
+static void set_format(ResampleParams&, const td_resample_src_job&, int) {}
+static void set_format(SrcParams& p, const td_resample_src_job& j, int ncols) {
+  p.fmt = j.fmt;
+  if (j.fmt == TD_SRC_RGB24) return;
+  const long long cw = (j.sw + 1) / 2, ch = (j.sh + 1) / 2, last = (long long)(j.T - 1) * j.frame_stride;
+  p.src_bytes = last + (long long)(j.sh - 1) * j.pitch0 + j.sw;
+  p.plane1 = (const unsigned char*)j.plane1; p.pitch1 = j.pitch1;
+  if (j.fmt == TD_SRC_NV12) {
+    p.bytes1 = last + (ch - 1) * j.pitch1 + 2 * cw;
+  } else {
+    p.bytes1 = last + (ch - 1) * j.pitch1 + cw;
+    p.plane2 = (const unsigned char*)j.plane2; p.pitch2 = j.pitch2;
+    p.bytes2 = last + (ch - 1) * j.pitch2 + cw;
+  }
+  p.nd = (ncols + 3 + 3) >> 2;  // + 3: the Y row is staged from its address rounded down to a dword
+  p.slot_bytes = (12 * p.nd + 15) & ~15;
+  const int* k = kYuvCoef[j.matrix][j.full_range];
+  p.yo = k[0]; p.cy = k[1]; p.crv = k[2]; p.cgu = k[3]; p.cgv = k[4]; p.cbu = k[5];
+}
 
-extern "C" size_t td_clip_resample_table_bytes(int n_jobs) { return n_jobs > 0 ? table_bytes(n_jobs) : 0; }
+// validation + job table + launch of both entry points; `legacy`: the jobs came through td_clip_resample (its messages)
+static const td_resample_src_job& widen(const td_resample_src_job& j) { return j; }
+static td_resample_src_job widen(const td_resample_job& j) {  // the same job in the wider record, format rgb24
+  td_resample_src_job s{};
+  s.plane0 = j.src; s.frame_stride = j.src_frame_stride; s.pitch0 = j.src_pitch;
+  s.fmt = TD_SRC_RGB24; s.T = j.T; s.sh = j.sh; s.sw = j.sw; s.flip = j.flip; s.rh = j.rh; s.rw = j.rw;
+  s.wy = j.wy; s.wx = j.wx; s.wh = j.wh; s.ww = j.ww;
+  s.dst = j.dst; s.planar = j.planar; s.frame_off = j.frame_off; s.H = j.H; s.W = j.W; s.mask = j.mask;
+  return s;
+}
 
-extern "C" int td_clip_resample(const td_resample_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes_, td_stream_t stream) {
-  TD_REQUIRE(jobs && n_jobs > 0 && n_jobs <= 65536, "td_clip_resample: no jobs (or more than 65536)");
-  TD_REQUIRE(table_host && table_dev && table_bytes_ >= td_clip_resample_table_bytes(n_jobs),
-             "td_clip_resample: job-table workspace missing or smaller than td_clip_resample_table_bytes(%d)", n_jobs);
-  ResampleParams* host = (ResampleParams*)table_host;
+template <typename P, typename J>
+static int enqueue(const char* who, bool legacy, const J* jobs, int n_jobs, void* table_host, void* table_dev, td_stream_t stream) {
+  P* host = (P*)table_host;
   int n = 0;
   long long blocks = 0;
   size_t lds = 0;
   for (int i = 0; i < n_jobs; i++) {
-    const td_resample_job& j = jobs[i];
-    TD_REQUIRE(j.T >= 0, "td_clip_resample: job %d has a negative frame count T = %d", i, j.T);
-    TD_REQUIRE(j.src && j.dst, "td_clip_resample: job %d has a null source or destination", i);
+    const td_resample_src_job j = widen(jobs[i]);
+    TD_REQUIRE(j.T >= 0, "%s: job %d has a negative frame count T = %d", who, i, j.T);
+    if (legacy) {
+      TD_REQUIRE(j.plane0 && j.dst, "%s: job %d has a null source or destination", who, i);
+    } else {
+      TD_REQUIRE(j.fmt == TD_SRC_RGB24 || j.fmt == TD_SRC_I420 || j.fmt == TD_SRC_NV12, "%s: job %d: unknown source format %d", who, i, j.fmt);
+      TD_REQUIRE(j.fmt == TD_SRC_RGB24 || ((j.matrix == TD_MATRIX_BT601 || j.matrix == TD_MATRIX_BT709) && (j.full_range == 0 || j.full_range == 1)),
+                 "%s: job %d: unknown colour matrix %d (or full_range %d is not 0 or 1)", who, i, j.matrix, j.full_range);
+      TD_REQUIRE(j.plane0, "%s: job %d: plane 0 is null", who, i);
+      TD_REQUIRE(j.fmt == TD_SRC_RGB24 || j.plane1, "%s: job %d: plane 1 is null", who, i);
+      TD_REQUIRE(j.fmt != TD_SRC_I420 || j.plane2, "%s: job %d: plane 2 is null", who, i);
+      TD_REQUIRE(j.dst, "%s: job %d has a null destination", who, i);
+    }
     TD_REQUIRE(j.sh > 0 && j.sw > 0 && j.rh > 0 && j.rw > 0 && j.sh <= kMaxSide && j.sw <= kMaxSrcCols && j.rh <= kMaxSide && j.rw <= kMaxSide,
-               "td_clip_resample: job %d: sizes %d x %d -> %d x %d outside 1..%d (source rows up to %d pixels)", i, j.sh, j.sw, j.rh, j.rw, kMaxSide, kMaxSrcCols);
+               "%s: job %d: sizes %d x %d -> %d x %d outside 1..%d (source rows up to %d pixels)", who, i, j.sh, j.sw, j.rh, j.rw, kMaxSide, kMaxSrcCols);
     TD_REQUIRE(j.wy >= 0 && j.wx >= 0 && j.wh > 0 && j.ww > 0 && j.wy + (long long)j.wh <= j.rh && j.wx + (long long)j.ww <= j.rw,
-               "td_clip_resample: job %d: window (%d, %d, %d, %d) outside the resized image %d x %d", i, j.wy, j.wx, j.wh, j.ww, j.rh, j.rw);
-    TD_REQUIRE(j.src_pitch >= 3 * j.sw && j.src_frame_stride >= (long long)j.src_pitch * (j.sh - 1) + 3 * j.sw,
-               "td_clip_resample: job %d: row pitch %d / frame stride %lld too small for %d x %d rgb24", i, j.src_pitch, j.src_frame_stride, j.sh, j.sw);
-    TD_REQUIRE(j.flip == 0 || j.flip == 1, "td_clip_resample: job %d: flip must be 0 or 1", i);
+               "%s: job %d: window (%d, %d, %d, %d) outside the resized image %d x %d", who, i, j.wy, j.wx, j.wh, j.ww, j.rh, j.rw);
+    if (legacy) {
+      TD_REQUIRE(j.pitch0 >= 3 * j.sw && j.frame_stride >= (long long)j.pitch0 * (j.sh - 1) + 3 * j.sw,
+                 "%s: job %d: row pitch %d / frame stride %lld too small for %d x %d rgb24", who, i, j.pitch0, j.frame_stride, j.sh, j.sw);
+    } else {
+      // row bytes and rows of each plane
+      const int cw = (j.sw + 1) / 2, ch = (j.sh + 1) / 2;
+      const int n_planes = j.fmt == TD_SRC_RGB24 ? 1 : j.fmt == TD_SRC_NV12 ? 2 : 3;
+      const int row_bytes[3] = {j.fmt == TD_SRC_RGB24 ? 3 * j.sw : j.sw, j.fmt == TD_SRC_NV12 ? 2 * cw : cw, cw};
+      const int rows[3] = {j.sh, ch, ch}, pitch[3] = {j.pitch0, j.pitch1, j.pitch2};
+      for (int k = 0; k < n_planes; k++)
+        TD_REQUIRE(pitch[k] >= row_bytes[k], "%s: job %d: pitch %d of plane %d is below its row of %d bytes", who, i, pitch[k], k, row_bytes[k]);
+      for (int k = 0; k < n_planes; k++)
+        TD_REQUIRE(j.frame_stride >= (long long)pitch[k] * (rows[k] - 1) + row_bytes[k],
+                   "%s: job %d: frame stride %lld is smaller than plane %d needs (%d rows of pitch %d)", who, i, j.frame_stride, k, rows[k], pitch[k]);
+    }
+    TD_REQUIRE(j.flip == 0 || j.flip == 1, "%s: job %d: flip must be 0 or 1", who, i);
     if (j.planar)
       TD_REQUIRE(j.mask && j.H >= j.wh && j.W >= j.ww && j.H <= kMaxSide && j.W <= kMaxSide && j.frame_off >= 0,
-                 "td_clip_resample: job %d: planar destination needs a mask, frame_off >= 0 and H x W = %d x %d >= the window %d x %d", i, j.H, j.W, j.wh, j.ww);
+                 "%s: job %d: planar destination needs a mask, frame_off >= 0 and H x W = %d x %d >= the window %d x %d", who, i, j.H, j.W, j.wh, j.ww);
     if (j.T == 0) continue;
-    ResampleParams p{};
-    p.src = (const unsigned char*)j.src; p.dst = (unsigned char*)j.dst; p.mask = (unsigned char*)j.mask;
-    p.src_frame_stride = j.src_frame_stride;
-    p.src_bytes = (long long)(j.T - 1) * j.src_frame_stride + (long long)(j.sh - 1) * j.src_pitch + 3LL * j.sw;
-    p.pitch = j.src_pitch; p.T = j.T; p.sh = j.sh; p.sw = j.sw; p.flip = j.flip; p.rh = j.rh; p.rw = j.rw;
+    P p{};
+    p.src = (const unsigned char*)j.plane0; p.dst = (unsigned char*)j.dst; p.mask = (unsigned char*)j.mask;
+    p.src_frame_stride = j.frame_stride;
+    p.src_bytes = (long long)(j.T - 1) * j.frame_stride + (long long)(j.sh - 1) * j.pitch0 + 3LL * j.sw;
+    p.pitch = j.pitch0; p.T = j.T; p.sh = j.sh; p.sw = j.sw; p.flip = j.flip; p.rh = j.rh; p.rw = j.rw;
     p.wy = j.wy; p.wx = j.wx; p.wh = j.wh; p.ww = j.ww;
     p.planar = j.planar ? 1 : 0; p.frame_off = j.frame_off;
     p.H = j.planar ? j.H : j.wh; p.W = j.planar ? j.W : j.ww;
@@ -248,24 +464,47 @@ extern "C" int td_clip_resample(const td_resample_job* jobs, int n_jobs, void* t
     p.cmin = j.flip ? j.sw - 1 - c_hi : c_lo;
     const int ncols = c_hi - c_lo + 1;
     p.slot_bytes = (3 * ncols + 3 + 15) & ~15;  // + 3: the row is staged from its address rounded down to a dword
+    set_format(p, j, ncols);                    // I420 / NV12: the Y plane's extent, the chroma planes, 12 bytes per staged Y dword
     const size_t fixed = (((size_t)p.W * sizeof(ColEntry) + kMaxBand * sizeof(RowEntry) + 2 * kMaxBand * sizeof(int)) + 15) & ~(size_t)15;
     p.R = kMaxBand;
     while (p.R > 1 && fixed + 2 * (size_t)p.R * p.slot_bytes > kMaxLds) p.R >>= 1;
     const size_t need = fixed + 2 * (size_t)p.R * p.slot_bytes;
-    TD_REQUIRE(need <= kMaxLds, "td_clip_resample: job %d needs %zu bytes of LDS (destination row of %d pixels, %d source columns)", i, need, p.W, ncols);
+    TD_REQUIRE(need <= kMaxLds, "%s: job %d needs %zu bytes of LDS (destination row of %d pixels, %d source columns)", who, i, need, p.W, ncols);
     lds = std::max(lds, need);
     p.nbands = cdiv(p.H, p.R);
     p.block_begin = (int)blocks;
     blocks += (long long)p.nbands * cdiv(p.T, kFrameChunk);
-    TD_REQUIRE(blocks < (1LL << 31), "td_clip_resample: too many workgroups");
+    TD_REQUIRE(blocks < (1LL << 31), "%s: too many workgroups", who);
     host[n++] = p;
   }
   if (n == 0) return TD_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(table_dev, host, (size_t)n * sizeof(ResampleParams), hipMemcpyHostToDevice, st) != hipSuccess) {
-    set_error("td_clip_resample: job table upload failed");
+  if (hipMemcpyAsync(table_dev, host, (size_t)n * sizeof(P), hipMemcpyHostToDevice, st) != hipSuccess) {
+    set_error("%s: job table upload failed", who);
     return TD_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL(clip_resample_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, st, (const ResampleParams*)table_dev, n);
-  return check_launch("td_clip_resample");
+  hipLaunchKernelGGL(clip_resample_kernel<P>, dim3((unsigned)blocks), dim3(kThreads), lds, st, (const P*)table_dev, n);
+  return check_launch(who);
+}
+
+}  // namespace td
+
+using namespace td;
+
+extern "C" size_t td_clip_resample_table_bytes(int n_jobs) { return n_jobs > 0 ? table_bytes<ResampleParams>(n_jobs) : 0; }
+
+extern "C" int td_clip_resample(const td_resample_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes_, td_stream_t stream) {
+  TD_REQUIRE(jobs && n_jobs > 0 && n_jobs <= 65536, "td_clip_resample: no jobs (or more than 65536)");
+  TD_REQUIRE(table_host && table_dev && table_bytes_ >= td_clip_resample_table_bytes(n_jobs),
+             "td_clip_resample: job-table workspace missing or smaller than td_clip_resample_table_bytes(%d)", n_jobs);
+  return enqueue<ResampleParams>("td_clip_resample", true, jobs, n_jobs, table_host, table_dev, stream);
+}
+
+extern "C" size_t td_clip_resample_src_table_bytes(int n_jobs) { return n_jobs > 0 ? table_bytes<SrcParams>(n_jobs) : 0; }
+
+extern "C" int td_clip_resample_src(const td_resample_src_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes_, td_stream_t stream) {
+  TD_REQUIRE(jobs && n_jobs > 0 && n_jobs <= 65536, "td_clip_resample_src: no jobs (or more than 65536)");
+  TD_REQUIRE(table_host && table_dev && table_bytes_ >= td_clip_resample_src_table_bytes(n_jobs),
+             "td_clip_resample_src: job-table workspace missing or smaller than td_clip_resample_src_table_bytes(%d)", n_jobs);
+  return enqueue<SrcParams>("td_clip_resample_src", false, jobs, n_jobs, table_host, table_dev, stream);
 }

@@ -102,27 +102,33 @@ class ClipPipeline:
         return slot
 
     def stage_raw(self, videos: Sequence, plans: Sequence, input_ids: torch.Tensor, attention_mask: torch.Tensor, inter_idx: List[List[int]]) -> dict:
-        """videos: one uint8 (T_i, h_i, w_i, 3) CPU array / tensor per video AS DECODED (rgb24 at the video's own size,
-        datasets/vidstg.py:109-115); plans: its ``ClipPlan`` (tubedetr_amd.augment: ``make_video_transforms(...).plan``).
+        """videos: per video its frames AS DECODED at the video's own size: a uint8 (T_i, h_i, w_i, 3) CPU array / tensor
+        (rgb24, datasets/vidstg.py:109-115) or a ``tubedetr_amd.augment.DecodedClip`` (the decoder's native yuv420p /
+        nv12 buffer: half the bytes, no colour conversion on the host; formats may be mixed); plans: its ``ClipPlan``
+        (tubedetr_amd.augment: ``make_video_transforms(...).plan``).
         Packs the decoded frames into page-locked memory, copies them ONCE on the copy stream and enqueues the resample
-        launches there (td_clip_resample: flip, resize, crop, second resize, padding and padding mask); the ticket is
-        what ``stage`` returns, so ``collect`` gives the same batch dict.  ``target_boxes`` are the annotated frames'
-        boxes of the plans.  Temporal cropping stays with the caller: slice the array (and the targets) before this."""
+        launches there (td_clip_resample / td_clip_resample_src: colour conversion, flip, resize, crop, second resize,
+        padding and padding mask; the launch that reads a clip converts it, the intermediate between the two training
+        resizes is rgb); the ticket is what ``stage`` returns, so ``collect`` gives the same batch dict.
+        ``target_boxes`` are the annotated frames' boxes of the plans.  Temporal cropping stays with the caller: slice
+        the array (and the targets) before this."""
         from . import _hip
-        from .augment import resample_job
+        from .augment import DecodedClip, resample_job, resample_src_job
 
         vids = []
         for v in videos:
-            v = torch.as_tensor(v)
-            assert v.dtype == torch.uint8 and v.dim() == 4 and v.shape[3] == 3 and not v.is_cuda, "videos are uint8 (T, h, w, 3) on the host"
-            vids.append(v.contiguous())
+            if not isinstance(v, DecodedClip):
+                v = torch.as_tensor(v)
+                assert v.dtype == torch.uint8 and v.dim() == 4 and v.shape[3] == 3 and not v.is_cuda, "videos are uint8 (T, h, w, 3) on the host, or DecodedClips"
+                v = DecodedClip(v, v.shape[0], v.shape[1], v.shape[2], "rgb24")
+            vids.append(v)
         assert len(vids) == len(plans) == len(inter_idx)
-        durations = [int(v.shape[0]) for v in vids]
+        durations = [v.T for v in vids]
         H, W = max(int(p.hw[0]) for p in plans), max(int(p.hw[1]) for p in plans)
         n = sum(durations)
         boxes = []
         for p, v, inter in zip(plans, vids, inter_idx):
-            assert len(p.targets) == v.shape[0] and tuple(p.src_hw) == tuple(v.shape[1:3]), "the plan was drawn for another clip"
+            assert len(p.targets) == v.T and tuple(p.src_hw) == (v.h, v.w), "the plan was drawn for another clip"
             if inter and inter[0] >= 0:  # number of boxes = number of frames in the annotated moment (datasets/vidstg.py:140-147)
                 n_boxed = len([t for t in p.targets if len(t["boxes"])])
                 assert n_boxed == inter[-1] - inter[0] + 1, (n_boxed, inter)
@@ -131,13 +137,20 @@ class ClipPipeline:
         offs, total = [], 0
         for v in vids:
             offs.append(total)
-            total += (v.numel() + 15) // 16 * 16
+            total += (v.nbytes + 15) // 16 * 16
         lib = _hip.lib()
-        n_first = sum(1 for p in plans if len(p.stages) == 2)
-        tb = [int(lib.td_clip_resample_table_bytes(n_first)), int(lib.td_clip_resample_table_bytes(len(plans)))]
+        # a launch whose jobs all read rgb24 is td_clip_resample's, as before there were other formats
+        yuv = [[v.pix_fmt != "rgb24" for v, p in zip(vids, plans) if len(p.stages) == 2], [v.pix_fmt != "rgb24" and len(p.stages) == 1 for v, p in zip(vids, plans)]]
+        tb = [int((lib.td_clip_resample_src_table_bytes if any(y) else lib.td_clip_resample_table_bytes)(len(y))) for y in yuv]
         raw_pin, tab_pin, _ = slot = self._raw_staging(total, tb[0] + tb[1])
         for v, o in zip(vids, offs):
-            raw_pin[o : o + v.numel()].copy_(v.view(-1))
+            raw_pin[o : o + v.nbytes].copy_(v.data)
+
+        def job(use_src, src, d, sh, sw, flip, stage, dst, fmt, **kw):
+            if use_src:
+                return resample_src_job(src, d, sh, sw, flip, stage, dst, *fmt, **kw)
+            return resample_job(src, d, sh, sw, flip, stage, dst, **kw)
+
         ragged = any(tuple(p.hw) != (H, W) for p in plans)
         valid_hw = []
         for p, d in zip(plans, durations):
@@ -156,22 +169,26 @@ class ClipPipeline:
             # hands their memory to later work of that stream alone, so they may go out of scope once the launches are enqueued
             first, final, keep, off = [], [], [], 0
             for v, p, o, d in zip(vids, plans, offs, durations):
-                src, sh, sw, flip = raw_dev.data_ptr() + o, int(v.shape[1]), int(v.shape[2]), p.flip
+                src, sh, sw, flip, fmt = raw_dev.data_ptr() + o, v.h, v.w, p.flip, (v.pix_fmt, v.matrix, v.full_range)
                 if len(p.stages) == 2:  # resize + crop into an interleaved uint8 intermediate (the reference rounds to uint8 there)
                     s = p.stages[0]
                     mid = torch.empty((d, s.wh, s.ww, 3), dtype=torch.uint8, device=self.device)
                     keep.append(mid)
-                    first.append(resample_job(src, d, sh, sw, flip, s, mid.data_ptr()))
-                    src, sh, sw, flip = mid.data_ptr(), s.wh, s.ww, False
+                    first.append(job(any(yuv[0]), src, d, sh, sw, flip, s, mid.data_ptr(), fmt))
+                    src, sh, sw, flip, fmt = mid.data_ptr(), s.wh, s.ww, False, ("rgb24", "bt601", False)
                 s = p.stages[-1]
                 assert (s.wh, s.ww) == tuple(p.hw)
-                final.append(resample_job(src, d, sh, sw, flip, s, vid_dev.data_ptr(), planar=True, frame_off=off, H=H, W=W, mask=msk_dev.data_ptr()))
+                final.append(job(any(yuv[1]), src, d, sh, sw, flip, s, vid_dev.data_ptr(), fmt, planar=True, frame_off=off, H=H, W=W, mask=msk_dev.data_ptr()))
                 off += d
             t_off = 0
-            for jobs, nb in ((first, tb[0]), (final, tb[1])):
+            for jobs, nb, src_fmt in ((first, tb[0], any(yuv[0])), (final, tb[1], any(yuv[1]))):
                 if jobs:
-                    arr = (_hip.ResampleJob * len(jobs))(*jobs)
-                    _hip.check(lib.td_clip_resample(arr, len(jobs), tab_pin.data_ptr() + t_off, tab_dev.data_ptr() + t_off, nb, _hip.stream_ptr()), "td_clip_resample")
+                    if src_fmt:
+                        arr = (_hip.ResampleSrcJob * len(jobs))(*jobs)
+                        _hip.check(lib.td_clip_resample_src(arr, len(jobs), tab_pin.data_ptr() + t_off, tab_dev.data_ptr() + t_off, nb, _hip.stream_ptr()), "td_clip_resample_src")
+                    else:
+                        arr = (_hip.ResampleJob * len(jobs))(*jobs)
+                        _hip.check(lib.td_clip_resample(arr, len(jobs), tab_pin.data_ptr() + t_off, tab_dev.data_ptr() + t_off, nb, _hip.stream_ptr()), "td_clip_resample")
                 t_off += nb
             idx_dev = torch.tensor(slow_idx, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
             vhw_dev = torch.tensor(valid_hw, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True) if ragged else None
