@@ -889,6 +889,91 @@ class ReplicateRowsFn(Function):
         return d_mem, None
 
 
+class RowGatherMap:
+    """out[i * m + j] = in[block_of[i] * m + j]: blocks of ``m`` rows taken through a block index that may repeat blocks, leave blocks out and
+    come in any order.  Built once on the host and kept on the device, like ReplicaMaps.
+
+      src               [n_out]    input row of every output row (td_rows_copy's source map)
+      seg_idx, seg_ptr  CSR lists "output rows that read this input row", in output order, for the backward (td_rows_segment_sum);
+                        an input block that no output names has empty segments, so its gradient rows are zeros"""
+
+    def __init__(self, block_of, n_blocks_in: int, m: int, device):
+        block_of = torch.as_tensor(block_of, dtype=torch.long).cpu()
+        assert block_of.numel() > 0 and int(block_of.min()) >= 0 and int(block_of.max()) < n_blocks_in, "block index outside the input"
+        i32 = lambda t_: t_.to(torch.int32).contiguous().to(device)
+        j = torch.arange(m)
+        self.m, self.n_in, self.n_out = m, n_blocks_in * m, block_of.numel() * m
+        assert max(self.n_in, self.n_out) < 2 ** 31
+        self.src = i32((block_of[:, None] * m + j[None, :]).reshape(-1))
+        order = torch.argsort(block_of, stable=True)
+        counts = torch.bincount(block_of, minlength=n_blocks_in)
+        starts = torch.cumsum(counts, 0) - counts
+        ptr = torch.zeros(self.n_in + 1, dtype=torch.long)
+        ptr[1:] = torch.cumsum(counts.repeat_interleave(m), 0)
+        idx = torch.empty(self.n_out, dtype=torch.long)
+        for blk in range(n_blocks_in):  # host work done once per pattern
+            users = order[starts[blk] : starts[blk] + counts[blk]]
+            part = (users[None, :] * m + j[:, None]).reshape(-1)  # [m, count] row-major: the segment of input row (blk, j) is contiguous
+            idx[ptr[blk * m] : ptr[blk * m] + part.numel()] = part
+        self.seg_idx, self.seg_ptr = i32(idx), i32(ptr)
+
+
+class PairMaps:
+    """Index vectors of a multi-sentence call: caption p refers to clip ``clip_index[p]`` (any order, repeats, clips that no caption names),
+    and everything behind the text-independent features sees P = len(clip_index) "videos" of durations ``durations[clip_index[p]]``.
+    Per clip there are n_clips slow clips and t_clip = max(durations) (time-padded) frames of hw tokens each; per pair n_clips slow clips
+    and t = max(pair durations) frames.
+
+      durations          per-pair durations (host list)
+      slow_of, frame_of  [P * n_clips] / [P * t] long: clip-level slow clip / frame of every pair-level one (pad masks are indexed with these)
+      slow, frames       RowGatherMap over the hw token rows of those blocks (activations: GatherRowsFn)
+      identity           clip_index is 0, 1, ..., C - 1: the pair rows ARE the clip rows and nothing is gathered"""
+
+    def __init__(self, durations, clip_index, stride: int, hw: int, device):
+        C, k = len(durations), int(stride)
+        ci = [int(c) for c in clip_index]
+        assert k > 0 and len(ci) > 0, "clip_index needs temporal sampling (stride > 0) and at least one caption"
+        if any(not 0 <= c < C for c in ci):
+            raise IndexError(f"clip_index {ci} names a clip outside the {C} clips of the batch")
+        self.clip_index = tuple(ci)
+        self.durations = [int(durations[c]) for c in ci]
+        t_clip, t = max(durations), max(self.durations)
+        n_clips = math.ceil(t_clip / k)
+        if math.ceil(t / k) != n_clips:
+            raise AssertionError("all videos of a batch must have the same number of slow clips (the clips the captions name are shorter than the batch's longest)")
+        self.P, self.C, self.t, self.t_clip, self.n_clips, self.hw = len(ci), C, t, t_clip, n_clips, hw
+        self.identity = ci == list(range(C))
+        cv = torch.tensor(ci, dtype=torch.long)
+        slow_of = (cv[:, None] * n_clips + torch.arange(n_clips)[None, :]).reshape(-1)
+        frame_of = (cv[:, None] * t_clip + torch.arange(t)[None, :]).reshape(-1)
+        self.slow_of, self.frame_of = slow_of.to(device), frame_of.to(device)
+        self.slow = RowGatherMap(slow_of, C * n_clips, hw, device)
+        self.frames = RowGatherMap(frame_of, C * t_clip, hw, device)
+
+
+class GatherRowsFn(Function):
+    """out = rows taken through a RowGatherMap (td_rows_copy): the per-clip rows of a multi-sentence call as per-pair rows.  Backward = the
+    segment sum over the pairs of each clip (td_rows_segment_sum): one thread per 16-byte run of a clip row adds its pairs' rows in pair
+    order with fp32 accumulation - no atomics, so the sum is bit-reproducible with or without td_set_deterministic, like ReplicateRowsFn's."""
+
+    @staticmethod
+    def forward(ctx, rows, gmap):
+        assert rows.dim() == 2 and rows.shape[0] == gmap.n_in, (tuple(rows.shape), gmap.n_in)
+        rows = rows.contiguous()
+        out = torch.empty((gmap.n_out, rows.shape[1]), dtype=rows.dtype, device=rows.device)
+        ops.rows_copy(rows, gmap.src, out, None, gmap.n_out)
+        ctx.gmap = gmap
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        gmap = ctx.gmap
+        g = g.contiguous()
+        d_rows = torch.empty((gmap.n_in, g.shape[1]), dtype=g.dtype, device=g.device)
+        ops.rows_segment_sum(g, gmap.seg_idx, gmap.seg_ptr, d_rows)
+        return d_rows, None
+
+
 class SlowFastAggregateFn(Function):
     """Temporal replication + slow-fast aggregation (transformer.py:393-445) producing the frame memory [F * S, d] directly:
 

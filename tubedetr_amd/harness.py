@@ -36,12 +36,20 @@ def batch_to(batch: dict, device) -> dict:
 
 def forward_step(model, criterion, weight_dict: Dict[str, float], batch: dict):
     """batch: frames (n_slow,3,H,W), frames_mask, frames_fast / fast_mask (or None), durations, target_boxes (sum dur, 4),
-    inter_idx; captions come from the model's tokenizer (set a FixedTokenizer for synthetic ids)."""
+    inter_idx; captions come from the model's tokenizer (set a FixedTokenizer for synthetic ids).
+    ``clip_index`` (optional, one clip number per caption): several captions per clip on one trunk pass; target_boxes, inter_idx and captions
+    are then per (clip, caption) pair and everything behind the encode call sees the pairs as the batch."""
     durations: List[int] = batch["durations"]
+    clip_index = batch.get("clip_index")
     samples = NestedTensor(batch["frames"], batch["frames_mask"])
     samples_fast = NestedTensor(batch["frames_fast"], batch["fast_mask"]) if batch.get("frames_fast") is not None else None
-    captions = batch.get("captions") or ["synthetic caption"] * len(durations)
-    memory_cache = model(samples, durations, captions, encode_and_save=True, samples_fast=samples_fast)
+    if clip_index is None:
+        captions = batch.get("captions") or ["synthetic caption"] * len(durations)
+        memory_cache = model(samples, durations, captions, encode_and_save=True, samples_fast=samples_fast)
+    else:
+        captions = batch.get("captions") or ["synthetic caption"] * len(clip_index)
+        memory_cache = model(samples, durations, captions, encode_and_save=True, samples_fast=samples_fast, clip_index=clip_index)
+        durations = [durations[c] for c in clip_index]
     outputs = model(samples, durations, captions, encode_and_save=False, memory_cache=memory_cache)
     raw = dict(outputs)
     raw["aux_outputs"] = [dict(a) for a in outputs.get("aux_outputs", [])]

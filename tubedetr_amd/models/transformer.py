@@ -319,6 +319,14 @@ class Transformer(nn.Module):
             hit = self._idx_cache[key] = Fk.ReplicaMaps(owner, n, hw, L, device)
         return hit
 
+    def _pair_maps(self, durations, clip_index, hw, device):
+        """Index vectors of a multi-sentence call (functional.PairMaps), built once per (durations, clip_index) pattern and kept on the device."""
+        key = ("pairs", tuple(durations), tuple(int(c) for c in clip_index), self.stride, hw, str(device))
+        hit = self._idx_cache.get(key)
+        if hit is None:
+            hit = self._idx_cache[key] = Fk.PairMaps(durations, clip_index, self.stride, hw, device)
+        return hit
+
     def _indices(self, durations, n_clips_per_video: int, device):
         """owner clip of every (video, frame) and the per-clip / per-frame video index; cached per durations."""
         key = (tuple(durations), n_clips_per_video, str(device))
@@ -393,25 +401,41 @@ class Transformer(nn.Module):
 
     def forward(self, src=None, mask=None, query_embed=None, pos_embed=None, text=None, encode_and_save=True, durations=None,
                 tpad_mask_t=None, fast_src=None, img_memory=None, query_mask=None, text_memory=None, text_mask=None,
-                memory_mask=None, pos_mask=None):
+                memory_mask=None, pos_mask=None, clip_index=None):
         if not self.pass_pos_and_query:
             # the reference sets pos_embed = None in this mode (transformer.py:242-248) and then concatenates it with the text
             # rows (:325, TypeError), and its decode branch adds to a `src` that is None (:463-469): the flag cannot complete a
             # step there either, so the same failure class is raised here instead of silently running something else
             raise TypeError("pass_pos_and_query=False: the reference's Transformer.forward fails in this mode (models/transformer.py:242-248 -> 325, 463-469)")
         if encode_and_save:
-            return self._encode(src, mask, query_embed, pos_embed, text, durations, tpad_mask_t, fast_src, pos_mask)
+            return self._encode(src, mask, query_embed, pos_embed, text, durations, tpad_mask_t, fast_src, pos_mask, clip_index)
         return self._decode(img_memory, mask, pos_embed, query_embed, query_mask)
 
     # ---- encode (transformer.py:195-460) ----
-    def _encode(self, src, mask, query_embed, pos_embed, text, durations, tpad_mask_t, fast_src, pos_mask=None):
+    def _encode(self, src, mask, query_embed, pos_embed, text, durations, tpad_mask_t, fast_src, pos_mask=None, clip_index=None):
         n, d, h, w = src.shape  # (n_clips_total, d, h, w) channels-last view of NHWC rows
         dev, dt = src.device, self.compute_dtype
         hw = h * w
+        src_rows = src.permute(0, 2, 3, 1).reshape(n * hw, d)  # zero-copy when src is channels-last
+        gather = None
+        if clip_index is not None:
+            # several captions per clip: src / masks / fast_src are per CLIP, caption p refers to clip clip_index[p].  The per-clip rows become
+            # per-pair rows through cached index vectors here, where the text comes in; below this block a pair is a video like any other.
+            if not self.stride or (self.fast and self.fast_mode not in FAST_MODES_IN_HIP):
+                raise NotImplementedError("clip_index is not supported with --stride 0 or a --fast_mode ablation variant")
+            pairs = self._pair_maps(durations, clip_index, hw, dev)
+            assert n == pairs.C * pairs.n_clips, "every video of the batch must yield the same number of slow clips"
+            durations = pairs.durations
+            if not pairs.identity:
+                gather = pairs
+                src_rows = Fk.GatherRowsFn.apply(src_rows, pairs.slow)
+                mask, tpad_mask_t = mask[pairs.slow_of], tpad_mask_t[pairs.frame_of]
+                pos_mask = pos_mask[pairs.slow_of] if pos_mask is not None else None
+                n = pairs.P * pairs.n_clips
         b, t = len(durations), max(durations)
         n_clips = math.ceil(t / self.stride) if self.stride else t  # stride 0 (dense ablation): one clip per frame, no replication
         assert n == b * n_clips, "every video of the batch must yield the same number of slow clips"
-        src_bm = src.permute(0, 2, 3, 1).reshape(n, hw, d)  # zero-copy when src is channels-last
+        src_bm = src_rows.view(n, hw, d)
         # all index / mask tensors of a (durations) pattern are built once and stay on the device: a host->device copy
         # inside the step is a stream synchronisation point
         owner, vid_of_clip, vid_of_frame, query_mask, clip_vid_list = self._indices(durations, n_clips, dev)
@@ -441,7 +465,10 @@ class Transformer(nn.Module):
             assert self.sine_pos is not None and pos_mask is not None, "pos_embed=None needs the sine encoding's pad mask (pos_mask)"
             pos_full = _ops.pos_sine(pos_mask, self.sine_pos[0], dt, self.sine_pos[1], rows=S)
         else:  # a positional tensor handed in by the caller (learned encodings, the dense --stride 0 path, external callers)
-            pos_bm = pos_embed.permute(0, 2, 3, 1).reshape(n, hw, d)
+            pos_rows = pos_embed.permute(0, 2, 3, 1).reshape(-1, d)
+            if gather is not None:
+                pos_rows = Fk.GatherRowsFn.apply(pos_rows, gather.slow)
+            pos_bm = pos_rows.view(n, hw, d)
             pos_full = torch.cat([pos_bm.to(dt), torch.zeros(n, L, d, dtype=dt, device=dev)], dim=1)
         key_pad = torch.cat([mask.flatten(1), text_mask_clip], dim=1).to(torch.uint8)  # [n, S], 1 = ignore
         if self.fast and self.fast_mode == "noslow":  # no space-text attention for this baseline (transformer.py:330-340)
@@ -463,8 +490,11 @@ class Transformer(nn.Module):
                 frames_pos = Fk.ReplicateRowsFn.apply(pos_full.reshape(n * S, d), maps).view(b * t, S, d)
             mem2d = mem.reshape(n * S, d)
             if self.fast and not variant:  # transformer.py:373-375,387,441-445: replication + aggregation in one GEMM
-                fs = fast_src.permute(0, 2, 3, 1).reshape(b * t * hw, d)
+                fs = fast_src.permute(0, 2, 3, 1).reshape(-1, d)
                 fast_mem = Fk.linear(fs.to(dt), self.fast_encoder.weight, self.fast_encoder.bias)
+                if gather is not None:  # projected once per clip frame, then taken per pair
+                    fast_mem = Fk.GatherRowsFn.apply(fast_mem, gather.frames)
+                assert fast_mem.shape[0] == b * t * hw
                 frames_mem = Fk.SlowFastAggregateFn.apply(mem2d, fast_mem, self.fast_residual.weight, self.fast_residual.bias, maps).view(b * t, S, d)
             else:
                 frames_mem = Fk.ReplicateRowsFn.apply(mem2d, maps).view(b * t, S, d)

@@ -56,6 +56,28 @@ def _one_tensor(x):
     return x
 
 
+class VideoFeatures:
+    """The text-independent half of an encode pass (``TubeDETR.encode_video``), per clip: what the trunk, ``input_proj`` and the pad-mask
+    bookkeeping produce before any caption is looked at.  Made under ``torch.no_grad()`` its tensors carry no graph, and the object can be kept
+    (per video id, say) and grounded against any number of captions: using it never writes into it.
+
+      src, mask      projected slow features (n_slow, d, h, w) channels-last view and their pad mask (n_slow, h, w)
+      pos            the positional operand: None for the sine encoding (generated from ``mask`` by td_pos_sine), else the tensor a learned or
+                     foreign encoding returned
+      fast_src       the fast branch's projected features, time-padded to (b * t, d, h, w); None without --fast
+      tpad_mask_t    pad mask of every (time-padded) frame (b * t, h, w), its "avoid empty masks" edit already made (on this object's own tensor)
+      durations, stride"""
+
+    __slots__ = ("src", "mask", "pos", "fast_src", "tpad_mask_t", "durations", "stride")
+
+    def __init__(self, src, mask, pos, fast_src, tpad_mask_t, durations, stride):
+        self.src, self.mask, self.pos, self.fast_src, self.tpad_mask_t = src, mask, pos, fast_src, tpad_mask_t
+        self.durations, self.stride = [int(d) for d in durations], int(stride)
+
+    def tensors(self):
+        return {k: getattr(self, k) for k in ("src", "mask", "pos", "fast_src", "tpad_mask_t") if torch.is_tensor(getattr(self, k))}
+
+
 class TubeDETR(nn.Module):
     def __init__(self, backbone, transformer, num_queries, aux_loss=False, video_max_len=200, stride=5, guided_attn=False,
                  fast=False, fast_mode="", sted=True, compute_dtype=torch.float32):
@@ -160,14 +182,45 @@ class TubeDETR(nn.Module):
             self._idx_cache[key] = dest.to(device)
         return self._idx_cache[key]
 
-    def forward(self, samples: NestedTensor, durations, captions, encode_and_save=True, memory_cache=None, samples_fast=None):
+    def forward(self, samples: NestedTensor, durations, captions, encode_and_save=True, memory_cache=None, samples_fast=None, *,
+                video_features=None, clip_index=None):
+        """``clip_index`` (a list of P clip numbers, one per caption, any order, repeats allowed): the P captions refer to the clips of
+        ``samples``, whose text-independent work is done once per clip; everything downstream sees P videos of durations
+        ``durations[clip_index[p]]``.  ``video_features`` (from ``encode_video``): the same with the kept features in place of ``samples``;
+        without ``clip_index`` caption p then refers to clip p."""
         if encode_and_save:
             assert memory_cache is None
-            if not isinstance(samples, NestedTensor):
-                samples = NestedTensor.from_tensor_list(samples)
-            return self._encode(samples, durations, captions, samples_fast)
+            if video_features is None and clip_index is None:
+                if not isinstance(samples, NestedTensor):
+                    samples = NestedTensor.from_tensor_list(samples)
+                return self._encode(samples, durations, captions, samples_fast)
+            vf = video_features if video_features is not None else self.encode_video(samples, durations, samples_fast)
+            self._check_shared_clips(vf.stride)
+            if clip_index is None:
+                clip_index = list(range(len(vf.durations)))
+            assert len(captions) == len(clip_index), "clip_index names one clip per caption"
+            return self._ground(vf, captions, clip_index)
         assert memory_cache is not None
         return self._decode(memory_cache)
+
+    def _check_shared_clips(self, stride=None):
+        """What ``encode_video`` / ``clip_index`` / ``video_features`` cover: the default model, --no_fast and --no_tsa."""
+        if not self.stride:
+            raise NotImplementedError("--stride 0 (no temporal sampling) is not supported with encode_video / clip_index / video_features")
+        if self.fast and self.fast_mode != "":
+            raise NotImplementedError(f"--fast_mode {self.fast_mode} is not supported with encode_video / clip_index / video_features")
+        if not self._joiner:
+            raise NotImplementedError("a backbone other than this package's Joiner (--backbone) is not supported with encode_video / clip_index / video_features")
+        if stride is not None and stride != self.stride:
+            raise ValueError(f"these VideoFeatures were made with --stride {stride}, the model has --stride {self.stride}")
+
+    def encode_video(self, samples, durations, samples_fast=None) -> VideoFeatures:
+        """The text-independent half of the encode pass: trunk (merged, de-duplicated or two passes, as in any step), ``input_proj`` on the slow and
+        the fast frames, pad masks.  Ground captions on the result with ``forward(None, None, captions, video_features=..., clip_index=...)``."""
+        self._check_shared_clips()
+        if not isinstance(samples, NestedTensor):
+            samples = NestedTensor.from_tensor_list(samples)
+        return self._video_features(samples, durations, samples_fast)
 
     def _encode_dense(self, samples, durations, captions):
         """--stride 0 (models/tubedetr.py:140-153): no temporal sampling - every frame is encoded with the text, videos shorter
@@ -195,6 +248,16 @@ class TubeDETR(nn.Module):
     def _encode(self, samples, durations, captions, samples_fast):
         if not self.stride:
             return self._encode_dense(samples, durations, captions)
+        return self._ground(self._video_features(samples, durations, samples_fast), captions, None)
+
+    def _ground(self, vf: VideoFeatures, captions, clip_index):
+        """The text-dependent half: the transformer's encode pass over the clips' features (per pair through index vectors when ``clip_index`` is given)."""
+        tpad_mask = vf.mask.clone()
+        tpad_mask[:, 0, 0] = False  # avoid empty masks
+        return self.transformer(vf.src, tpad_mask, self.query_embed.weight, vf.pos, captions, encode_and_save=True, durations=vf.durations,
+                                tpad_mask_t=vf.tpad_mask_t, fast_src=vf.fast_src, pos_mask=vf.mask if vf.pos is None else None, clip_index=clip_index)
+
+    def _video_features(self, samples, durations, samples_fast) -> VideoFeatures:
         b, t, k = len(durations), max(durations), self.stride
         # sine encoding: the transformer forms the positional operand from the (original) pad mask itself, see Joiner.forward
         want_pos = not self._sine_pos
@@ -269,11 +332,8 @@ class TubeDETR(nn.Module):
         else:  # frames inherit the mask of their slow clip (tubedetr.py:172-178)
             clip_of = torch.cat([i * n_clips + torch.arange(d) // k for i, d in enumerate(durations)]).to(dev)
             tpad_mask_t[dest] = mask[clip_of]
-        tpad_mask = mask.clone()
-        tpad_mask[:, 0, 0] = False  # avoid empty masks
-        tpad_mask_t[:, 0, 0] = False
-        return self.transformer(src, tpad_mask, self.query_embed.weight, pos[-1], captions, encode_and_save=True,
-                                durations=durations, tpad_mask_t=tpad_mask_t, fast_src=fast_src, pos_mask=None if want_pos else mask)
+        tpad_mask_t[:, 0, 0] = False  # avoid empty masks (tpad_mask_t is this call's own tensor: a fresh one or a clone)
+        return VideoFeatures(src, mask, pos[-1] if want_pos else None, fast_src, tpad_mask_t, durations, k)
 
     def _decode(self, memory_cache):
         res = self.transformer(img_memory=memory_cache["img_memory"], mask=memory_cache["mask"], pos_embed=memory_cache["pos_embed"],
