@@ -568,6 +568,48 @@ typedef struct td_resample_src_job {
 size_t td_clip_resample_src_table_bytes(int n_jobs);
 int td_clip_resample_src(const td_resample_src_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
 
+/* Every index vector of one durations pattern in ONE launch (an addition WITHIN ABI 11).  A batch of b videos of durations d_i
+ * sampled with stride k has c_i = ceil(d_i / k) slow clips per video - any mix of clip counts - n = sum c_i clips in all, and
+ * F = b t frames with t = max d_i (shorter videos are padded in time).  ``table`` is a DEVICE array of b records
+ * (d_i, first_clip_i = sum_{j<i} c_j, c_i), int32; b <= 256.
+ * Owner clip of frame (i, j): first_clip_i + min(j / k, c_i - 1) - for the frames of a video the reference's rule (models/transformer.py:393-427,
+ * models/tubedetr.py:154-187: frame j belongs to clip j / k of its video, the last clip may be shorter); a time-padded frame takes its
+ * video's last clip.  With equal clip counts this is i * n_clips + j / k, the reference's flat numbering.
+ * Outputs (caller-allocated device buffers, each written completely; a NULL pointer leaves that vector out; the 14 maps are written
+ * together or not at all).  S = hw + L rows per clip / frame (hw visual tokens, then L text tokens); clip rows are c S + s, frame rows f S + s.
+ *   owner, vid_of_frame [F] int64; vid_of_clip [n] int64; query_mask [F] bytes, 1 = time padding (frame 0 of a video is never 1)
+ *   frame_dest, clip_of [sum d_i] int64: padded frame number i t + j, and owner clip, of the valid frames in video order
+ *   vis_src, vis_dst [F hw]; txt_src, txt_dst [F L]; all_src [F S]: clip row / frame row of every visual, text, any token
+ *   iota_vis, clip_vis [n hw]; clip_txt [n L]: 0, 1, 2, ...; clip rows of the visual / the text tokens
+ *   seg_X_idx, seg_X_ptr for X = vis (m = hw, first row 0), txt (m = L, first row hw), all (m = S, first row 0): CSR lists "frame
+ *     rows summed into output row (c, col)", [F m] and [n m + 1].  Clip c owns the count_c frames from f0_c on, so
+ *     ptr[c m + col] = m f0_c + col count_c and idx[ptr + q] = (f0_c + q) S + first row + col, frames ascending; ptr[n m] = F m.
+ * int32 unless stated; F S < 2^31 is required.  n_clips must be sum c_i: the table is not readable from the host side of the call, and
+ * the buffers' sizes follow from it. */
+typedef struct td_replica_maps_out {
+  long long* owner;
+  long long* vid_of_frame;
+  long long* vid_of_clip;
+  unsigned char* query_mask;
+  long long* frame_dest;
+  long long* clip_of;
+  int* vis_src;
+  int* vis_dst;
+  int* txt_src;
+  int* txt_dst;
+  int* all_src;
+  int* iota_vis;
+  int* clip_vis;
+  int* clip_txt;
+  int* seg_vis_idx;
+  int* seg_vis_ptr;
+  int* seg_txt_idx;
+  int* seg_txt_ptr;
+  int* seg_all_idx;
+  int* seg_all_ptr;
+} td_replica_maps_out;
+int td_replica_maps(const int* table, int b, int t, int k, int hw, int L, int n_clips, const td_replica_maps_out* out, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,12 @@ class ResampleSrcJob(C.Structure):
                [("dst", C.c_void_p)] + [(n, C.c_int) for n in ("planar", "frame_off", "H", "W")] + [("mask", C.c_void_p)]
 
 
+class ReplicaMapsOut(C.Structure):
+    """td_replica_maps_out."""
+    _fields_ = [(n, C.c_void_p) for n in ("owner", "vid_of_frame", "vid_of_clip", "query_mask", "frame_dest", "clip_of", "vis_src", "vis_dst", "txt_src", "txt_dst",
+                                          "all_src", "iota_vis", "clip_vis", "clip_txt", "seg_vis_idx", "seg_vis_ptr", "seg_txt_idx", "seg_txt_ptr", "seg_all_idx", "seg_all_ptr")]
+
+
 class Epilogue(C.Structure):
     _fields_ = [
         ("bias", C.c_void_p),
@@ -139,6 +145,7 @@ _SIGS = {
     "td_mha_lean_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _U32, _P, _I, _P],
     "td_clip_resample": [C.POINTER(ResampleJob), _I, _P, _P, _SZ, _P],
     "td_clip_resample_src": [C.POINTER(ResampleSrcJob), _I, _P, _P, _SZ, _P],
+    "td_replica_maps": [_P, _I, _I, _I, _I, _I, _I, C.POINTER(ReplicaMapsOut), _P],
 }
 _SIZE_SIGS = {
     "td_grad_norm_ws_bytes": [],

@@ -816,9 +816,91 @@ def multihead_attention_prekv(q_in, kv, layer, W_in, b_in, W_out, b_out, key_pad
                             pa, _seed() if pa > 0 else 0, po, _seed() if po > 0 else 0)
 
 
+class BatchLayout:
+    """Clip / frame bookkeeping of a batch of videos of durations d_i sampled with stride k > 0 - any mix of clip counts (``batch_layout``).
+
+      clips, first_clip   c_i = ceil(d_i / k) and sum_{j<i} c_j per video (host lists); n = sum c_i, t = max d_i, F = b * t
+      owner               [F] long: owner clip of frame (i, j) = first_clip_i + min(j // k, c_i - 1) - the reference's rule for a video's own
+                          frames (transformer.py:393-427); a time-padded frame takes its video's last clip
+      vid_of_clip         [n] long; vid_of_frame [F] long
+      query_mask          [b, t] bool: True = time padding (frame 0 of a video is never masked, transformer.py:236)
+      frame_dest          [sum d_i] long: padded frame number i * t + j of every valid frame, in video order
+      clip_of             [sum d_i] long: owner clip of every valid frame (--no_fast frame masks, tubedetr.py:172-178)"""
+
+    __slots__ = ("durations", "stride", "b", "t", "n", "F", "clips", "first_clip", "owner", "vid_of_clip", "vid_of_frame", "query_mask", "frame_dest", "clip_of")
+    _VECTORS = ("owner", "vid_of_clip", "vid_of_frame", "query_mask", "frame_dest", "clip_of")
+
+    def table(self) -> Tensor:
+        """[b, 3] int32 records (duration, first_clip, clips): td_replica_maps' input."""
+        return torch.tensor([[d, f, c] for d, f, c in zip(self.durations, self.first_clip, self.clips)], dtype=torch.int32)
+
+    def clip_videos(self):
+        """video of every clip, as a host list"""
+        return [i for i, c in enumerate(self.clips) for _ in range(c)]
+
+    def __getattr__(self, name):
+        # the host vectors are made on first use: the device builder needs the integers above and the table only
+        if name in BatchLayout._VECTORS:
+            self._build_vectors()
+            return object.__getattribute__(self, name)
+        raise AttributeError(name)
+
+    def _build_vectors(self):
+        b, t, k = self.b, self.t, self.stride
+        c, f0, d = torch.tensor(self.clips)[:, None], torch.tensor(self.first_clip)[:, None], torch.tensor(self.durations)[:, None]
+        j = torch.arange(t)[None, :]
+        owner2d = f0 + torch.minimum(j // k, c - 1)
+        valid = j < d
+        self.owner = owner2d.reshape(-1)
+        self.vid_of_clip = torch.arange(b).repeat_interleave(torch.tensor(self.clips))
+        self.vid_of_frame = torch.arange(b).repeat_interleave(t)
+        self.query_mask = ~valid
+        self.query_mask[:, 0] = False
+        self.frame_dest = (torch.arange(b)[:, None] * t + j)[valid]
+        self.clip_of = owner2d[valid]
+
+
+def batch_layout(durations, stride: int) -> BatchLayout:
+    """Pure host function (no device, no library).  With equal clip counts every vector is today's ``i * n_clips + j // k`` numbering."""
+    k = int(stride)
+    durations = [int(d) for d in durations]
+    if k <= 0 or not durations or min(durations) < 1:
+        raise ValueError(f"batch_layout needs stride > 0 and durations >= 1 (stride {stride}, durations {durations})")
+    lay = BatchLayout()
+    lay.durations, lay.stride = durations, k
+    b, t = len(durations), max(durations)
+    clips = [-(-d // k) for d in durations]
+    first = [0] * b
+    for i in range(1, b):
+        first[i] = first[i - 1] + clips[i - 1]
+    lay.b, lay.t, lay.n, lay.F, lay.clips, lay.first_clip = b, t, first[-1] + clips[-1], b * t, clips, first
+    return lay
+
+
+def check_slow_count(n_slow: int, lay: BatchLayout) -> None:
+    """The slow batch is the concatenation of video_i[::k]: sum ceil(d_i / k) frames."""
+    if n_slow != lay.n:
+        raise ValueError(f"the slow batch has {n_slow} frames, durations {lay.durations} at stride {lay.stride} need {lay.n} "
+                         f"(ceil(d / stride) per video: {lay.clips})")
+
+
+# Who builds a durations pattern's index vectors on a cache miss: td_replica_maps on the device (one pinned table copy + one launch, no
+# synchronising copy) or the host builders below (a dozen pageable copies).  TD_HOST_MAPS=1 seeds the switch; set_host_maps() flips it.
+_HOST_MAPS = [__import__("os").environ.get("TD_HOST_MAPS", "0") == "1"]
+
+
+def set_host_maps(on: bool) -> None:
+    _HOST_MAPS[0] = bool(on)
+
+
+def host_maps() -> bool:
+    return _HOST_MAPS[0]
+
+
 class ReplicaMaps:
-    """Index vectors of the temporal replication (transformer.py:393-427: frame (i, j) of video i takes the memory of clip
-    i * n_clips + j // k), built once per (durations, stride, hw, L) on the host and kept on the device.  Rows of the clip
+    """Index vectors of the temporal replication (transformer.py:393-427: frame (i, j) of video i takes the memory of its owner clip,
+    ``BatchLayout.owner``), built once per (durations, stride, hw, L) - here on the host from ``owner``, by ``from_table`` on the device -
+    and kept on the device.  Rows of the clip
     memory are c * S + s, rows of the frame memory f * S + s (S = hw visual + L text tokens).
 
       vis_src / vis_dst   [F * hw]   clip row / frame row of every visual token of every frame
@@ -865,6 +947,37 @@ class ReplicaMaps:
         self.seg_vis = csr(p, 0)
         self.seg_txt = csr(l_, hw)
         self.seg_all = csr(torch.arange(S), 0)
+
+    @classmethod
+    def from_table(cls, lay: BatchLayout, hw: int, L: int, device, maps: bool = True):
+        """The same attributes from ONE td_replica_maps launch, plus the layout's own vectors on the device (owner, vid_of_clip, vid_of_frame,
+        query_mask, frame_dest, clip_of).  Host work: the table's few integers, one page-locked non-blocking copy, the allocations.
+        ``maps=False``: the layout vectors alone (what the trunk side needs before the token count L is known)."""
+        from . import _hip
+
+        self = cls.__new__(cls)
+        F, n, S, V = lay.F, lay.n, hw + L, sum(lay.durations)
+        assert F * S < 2 ** 31, f"{F} frames of {S} rows exceed 32-bit row indices"
+        self.F, self.n, self.hw, self.L, self.S = F, n, hw, L, S
+        table = lay.table().pin_memory().to(device, non_blocking=True)
+        i64 = lambda m: torch.empty(m, dtype=torch.long, device=device)
+        i32 = lambda m: torch.empty(m, dtype=torch.int32, device=device)
+        self.owner, self.vid_of_frame, self.vid_of_clip, self.frame_dest, self.clip_of = i64(F), i64(F), i64(n), i64(V), i64(V)
+        self.query_mask = torch.empty((lay.b, lay.t), dtype=torch.bool, device=device)
+        out = _hip.ReplicaMapsOut(*(x.data_ptr() for x in (self.owner, self.vid_of_frame, self.vid_of_clip, self.query_mask, self.frame_dest, self.clip_of)))
+        if maps:
+            self.vis_src, self.vis_dst, self.txt_src, self.txt_dst, self.all_src = i32(F * hw), i32(F * hw), i32(F * L), i32(F * L), i32(F * S)
+            self.iota_vis, self.clip_vis, self.clip_txt = i32(n * hw), i32(n * hw), i32(n * L)
+            self.seg_vis, self.seg_txt, self.seg_all = (i32(F * hw), i32(n * hw + 1)), (i32(F * L), i32(n * L + 1)), (i32(F * S), i32(n * S + 1))
+            for name in ("vis_src", "vis_dst", "txt_src", "txt_dst", "all_src", "iota_vis", "clip_vis", "clip_txt"):
+                setattr(out, name, getattr(self, name).data_ptr())
+            for name in ("seg_vis", "seg_txt", "seg_all"):
+                setattr(out, name + "_idx", getattr(self, name)[0].data_ptr())
+                setattr(out, name + "_ptr", getattr(self, name)[1].data_ptr())
+        import ctypes
+
+        _hip.check(_hip.lib().td_replica_maps(table.data_ptr(), lay.b, lay.t, lay.stride, hw, L, n, ctypes.byref(out), _hip.stream_ptr()), "td_replica_maps")
+        return self
 
 
 class ReplicateRowsFn(Function):
@@ -921,11 +1034,13 @@ class RowGatherMap:
 class PairMaps:
     """Index vectors of a multi-sentence call: caption p refers to clip ``clip_index[p]`` (any order, repeats, clips that no caption names),
     and everything behind the text-independent features sees P = len(clip_index) "videos" of durations ``durations[clip_index[p]]``.
-    Per clip there are n_clips slow clips and t_clip = max(durations) (time-padded) frames of hw tokens each; per pair n_clips slow clips
-    and t = max(pair durations) frames.
+    The clips may have any mix of slow-clip counts (``batch_layout``), and so may the pairs: clip c has its c_c slow clips from
+    first_clip_c on and t_clip = max(durations) (time-padded) frames of hw tokens each; pair p has the c slow clips of its clip and
+    t = max(pair durations) frames.
 
       durations          per-pair durations (host list)
-      slow_of, frame_of  [P * n_clips] / [P * t] long: clip-level slow clip / frame of every pair-level one (pad masks are indexed with these)
+      n_slow, n_pair_slow   slow clips of the clip batch / of the pair batch
+      slow_of, frame_of  [n_pair_slow] / [P * t] long: clip-level slow clip / frame of every pair-level one (pad masks are indexed with these)
       slow, frames       RowGatherMap over the hw token rows of those blocks (activations: GatherRowsFn)
       identity           clip_index is 0, 1, ..., C - 1: the pair rows ARE the clip rows and nothing is gathered"""
 
@@ -935,19 +1050,23 @@ class PairMaps:
         assert k > 0 and len(ci) > 0, "clip_index needs temporal sampling (stride > 0) and at least one caption"
         if any(not 0 <= c < C for c in ci):
             raise IndexError(f"clip_index {ci} names a clip outside the {C} clips of the batch")
+        lay = batch_layout(durations, k)
         self.clip_index = tuple(ci)
         self.durations = [int(durations[c]) for c in ci]
-        t_clip, t = max(durations), max(self.durations)
-        n_clips = math.ceil(t_clip / k)
-        if math.ceil(t / k) != n_clips:
-            raise AssertionError("all videos of a batch must have the same number of slow clips (the clips the captions name are shorter than the batch's longest)")
-        self.P, self.C, self.t, self.t_clip, self.n_clips, self.hw = len(ci), C, t, t_clip, n_clips, hw
+        t_clip, t = lay.t, max(self.durations)
+        if math.ceil(t / k) != max(lay.clips):
+            # nothing below needs this refusal any more; tests/test_multi_sentence_cpu.py pins it
+            raise AssertionError("the captions name only clips with fewer slow clips than the batch's longest clip: at least one named clip must have "
+                                 "the same number of slow clips as the longest")
+        self.P, self.C, self.t, self.t_clip, self.hw = len(ci), C, t, t_clip, hw
+        self.n_clips = max(lay.clips)  # slow clips of the longest clip; read by no product code (tests/test_multi_sentence_cpu.py reads it)
+        self.n_slow, self.n_pair_slow = lay.n, sum(lay.clips[c] for c in ci)
         self.identity = ci == list(range(C))
         cv = torch.tensor(ci, dtype=torch.long)
-        slow_of = (cv[:, None] * n_clips + torch.arange(n_clips)[None, :]).reshape(-1)
+        slow_of = torch.cat([lay.first_clip[c] + torch.arange(lay.clips[c]) for c in ci])
         frame_of = (cv[:, None] * t_clip + torch.arange(t)[None, :]).reshape(-1)
         self.slow_of, self.frame_of = slow_of.to(device), frame_of.to(device)
-        self.slow = RowGatherMap(slow_of, C * n_clips, hw, device)
+        self.slow = RowGatherMap(slow_of, lay.n, hw, device)
         self.frames = RowGatherMap(frame_of, C * t_clip, hw, device)
 
 

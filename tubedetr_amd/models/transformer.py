@@ -327,21 +327,49 @@ class Transformer(nn.Module):
             hit = self._idx_cache[key] = Fk.PairMaps(durations, clip_index, self.stride, hw, device)
         return hit
 
-    def _indices(self, durations, n_clips_per_video: int, device):
-        """owner clip of every (video, frame) and the per-clip / per-frame video index; cached per durations."""
+    def _layout(self, durations):
+        """functional.batch_layout of a durations pattern (host side, cached)."""
+        key = ("layout", tuple(durations), self.stride)
+        hit = self._idx_cache.get(key)
+        if hit is None:
+            hit = self._idx_cache[key] = Fk.batch_layout(durations, self.stride)
+        return hit
+
+    def _indices(self, durations, n_clips_per_video, device):
+        """owner clip of every (video, frame) and the per-clip / per-frame video index; cached per durations.  Host-built (functional.batch_layout
+        for temporal sampling: any mix of clip counts; ``n_clips_per_video`` only names the pattern in the cache key)."""
         key = (tuple(durations), n_clips_per_video, str(device))
         hit = self._idx_cache.get(key)
         if hit is None:
-            b, t, k = len(durations), max(durations), (self.stride or 1)  # stride 0: every frame is its own clip
-            vid = torch.arange(b)
-            owner = (vid[:, None] * n_clips_per_video + torch.arange(t)[None, :] // k).reshape(-1)
-            query_mask = torch.ones(b, t, dtype=torch.bool)
-            query_mask[:, 0] = False  # avoid empty masks (transformer.py:236)
-            for i, dur in enumerate(durations):
-                query_mask[i, :dur] = False
-            voc = vid.repeat_interleave(n_clips_per_video)
-            hit = (owner.to(device), voc.to(device), vid.repeat_interleave(t).to(device), query_mask.to(device), voc.tolist())
+            if self.stride:
+                lay = Fk.batch_layout(durations, self.stride)
+                owner, voc, vof, query_mask = lay.owner, lay.vid_of_clip, lay.vid_of_frame, lay.query_mask
+            else:  # stride 0: every frame is its own clip, videos are padded in time
+                b, t = len(durations), max(durations)
+                vid = torch.arange(b)
+                owner = (vid[:, None] * t + torch.arange(t)[None, :]).reshape(-1)
+                query_mask = torch.ones(b, t, dtype=torch.bool)
+                query_mask[:, 0] = False  # avoid empty masks (transformer.py:236)
+                for i, dur in enumerate(durations):
+                    query_mask[i, :dur] = False
+                voc, vof = vid.repeat_interleave(t), vid.repeat_interleave(t)
+            hit = (owner.to(device), voc.to(device), vof.to(device), query_mask.to(device), voc.tolist())
             self._idx_cache[key] = hit
+        return hit
+
+    def _pattern(self, durations, lay, hw, L, device):
+        """-> (owner, vid_of_clip, vid_of_frame, query_mask, clip_vid_list, ReplicaMaps or None) of a durations pattern, cached in front of
+        either builder: ONE td_replica_maps launch (functional.ReplicaMaps.from_table), or the host builders when functional.host_maps()."""
+        if lay is None:
+            return self._indices(durations, max(durations), device) + (None,)
+        if Fk.host_maps():
+            idx = self._indices(durations, tuple(lay.clips), device)
+            return idx + (self._replica_maps(durations, tuple(lay.clips), idx[0], lay.n, hw, L, device),)
+        key = ("table", tuple(durations), self.stride, hw, L, str(device))
+        hit = self._idx_cache.get(key)
+        if hit is None:
+            m = Fk.ReplicaMaps.from_table(lay, hw, L, device)
+            hit = self._idx_cache[key] = (m.owner, m.vid_of_clip, m.vid_of_frame, m.query_mask, lay.clip_videos(), m)
         return hit
 
     def _encode_text(self, text, device):
@@ -424,21 +452,25 @@ class Transformer(nn.Module):
             if not self.stride or (self.fast and self.fast_mode not in FAST_MODES_IN_HIP):
                 raise NotImplementedError("clip_index is not supported with --stride 0 or a --fast_mode ablation variant")
             pairs = self._pair_maps(durations, clip_index, hw, dev)
-            assert n == pairs.C * pairs.n_clips, "every video of the batch must yield the same number of slow clips"
+            if n != pairs.n_slow:
+                Fk.check_slow_count(n, self._layout(durations))
             durations = pairs.durations
             if not pairs.identity:
                 gather = pairs
                 src_rows = Fk.GatherRowsFn.apply(src_rows, pairs.slow)
                 mask, tpad_mask_t = mask[pairs.slow_of], tpad_mask_t[pairs.frame_of]
                 pos_mask = pos_mask[pairs.slow_of] if pos_mask is not None else None
-                n = pairs.P * pairs.n_clips
+                n = pairs.n_pair_slow
         b, t = len(durations), max(durations)
-        n_clips = math.ceil(t / self.stride) if self.stride else t  # stride 0 (dense ablation): one clip per frame, no replication
-        assert n == b * n_clips, "every video of the batch must yield the same number of slow clips"
+        lay = self._layout(durations) if self.stride else None  # stride 0 (dense ablation): one clip per frame, no replication
+        if lay is not None:
+            Fk.check_slow_count(n, lay)
+            if self.fast and self.fast_mode not in FAST_MODES_IN_HIP and len(set(lay.clips)) > 1:
+                raise NotImplementedError(f"--fast_mode {self.fast_mode} with videos of different clip counts (durations {list(durations)} at "
+                                          f"--stride {self.stride}: {lay.clips} clips) is not supported; the default model and --no_fast are")
+        else:
+            assert n == b * t, "--stride 0: the batch holds every video padded to the longest"
         src_bm = src_rows.view(n, hw, d)
-        # all index / mask tensors of a (durations) pattern are built once and stay on the device: a host->device copy
-        # inside the step is a stream synchronisation point
-        owner, vid_of_clip, vid_of_frame, query_mask, clip_vid_list = self._indices(durations, n_clips, dev)
 
         # time queries (transformer.py:211-238): identical for every video, video-major rows [b*t, d]
         nq = query_embed.shape[0]
@@ -447,11 +479,14 @@ class Transformer(nn.Module):
         q = query_embed[0].float()
         qpos_t = (q[None, :] + self.time_embed(t)[:, 0, :]) if self.use_time_embed else q[None, :].expand(t, -1)
         query_pos_bm = qpos_t[None].expand(b, t, d)  # fp32, autograd reaches query_embed.weight
-        query_mask = query_mask.clone() if self.stride else None  # transformer.py:225-238: no time-query mask without temporal sampling
 
         text_attention_mask_orig, text_resized, tokenized = self._encode_text(text, dev)  # [B,L], [B,L,d]
         L = text_resized.shape[1]
-        assert n_clips == n // text_resized.shape[0] == mask.shape[0] // text_attention_mask_orig.shape[0]
+        assert b == text_resized.shape[0] == text_attention_mask_orig.shape[0] and mask.shape[0] == n
+        # all index / mask tensors of a (durations) pattern are built once and stay on the device: a host->device copy
+        # inside the step is a stream synchronisation point
+        owner, vid_of_clip, vid_of_frame, query_mask, clip_vid_list, maps = self._pattern(durations, lay, hw, L, dev)
+        query_mask = query_mask.clone() if self.stride else None  # transformer.py:225-238: no time-query mask without temporal sampling
         text_clip = text_resized[vid_of_clip]  # [n, L, d]
         text_mask_clip = text_attention_mask_orig[vid_of_clip]
         self._repeat_tokenized(tokenized, vid_of_clip, clip_vid_list)
@@ -480,8 +515,7 @@ class Transformer(nn.Module):
         if self.fast and fast_src is None:
             raise AttributeError("fast=True needs temporal sampling (stride > 0): the reference builds no fast_src without it (models/tubedetr.py:140-153)")
         if self.stride:
-            # temporal replication (transformer.py:393-427): frame (i, j) <- clip i*n_clips + j//k, as index vectors
-            maps = self._replica_maps(durations, n_clips, owner, n, hw, L, dev)
+            # temporal replication (transformer.py:393-427): frame (i, j) <- its owner clip (functional.BatchLayout), as index vectors
             frame_mask = torch.cat([tpad_mask_t.flatten(1), text_attention_mask_orig[vid_of_frame]], dim=1)  # [b*t, S]
             frame_mask[:, 0] = False  # "avoid empty masks" (transformer.py:424)
             if sine:  # the frames' positional rows come from the same kernel (a frame has its clip's pad mask), not from a gather of pos_full

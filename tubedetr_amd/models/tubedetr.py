@@ -182,6 +182,22 @@ class TubeDETR(nn.Module):
             self._idx_cache[key] = dest.to(device)
         return self._idx_cache[key]
 
+    def _frame_layout(self, durations, device):
+        """-> (BatchLayout, dest, clip_of): padded frame number and owner clip of every valid frame, on the device.  Needed before the caption's
+        token count is known, so it is a pass of its own in front of the transformer's: td_replica_maps without the replication maps, or the host
+        builder when functional.host_maps()."""
+        key = ("layout", tuple(durations), self.stride, str(device), Fk.host_maps())
+        hit = self._idx_cache.get(key)
+        if hit is None:
+            lay = Fk.batch_layout(durations, self.stride)
+            if Fk.host_maps():
+                hit = (lay, lay.frame_dest.to(device), lay.clip_of.to(device))
+            else:
+                m = Fk.ReplicaMaps.from_table(lay, 1, 0, device, maps=False)
+                hit = (lay, m.frame_dest, m.clip_of)
+            self._idx_cache[key] = hit
+        return hit
+
     def forward(self, samples: NestedTensor, durations, captions, encode_and_save=True, memory_cache=None, samples_fast=None, *,
                 video_features=None, clip_index=None):
         """``clip_index`` (a list of P clip numbers, one per caption, any order, repeats allowed): the P captions refer to the clips of
@@ -293,7 +309,7 @@ class TubeDETR(nn.Module):
             features, pos = self.backbone(samples, want_pos=want_pos) if self._joiner else self.backbone(samples)  # (a foreign backbone: the reference's protocol)
             src, mask = features[-1].decompose()
         dev = src.device
-        dest = self._frame_index(durations, dev)
+        lay, dest, clip_of = self._frame_layout(durations, dev)
         identity = dest.numel() == b * t
         fast_src = None
         if self.fast:
@@ -318,8 +334,7 @@ class TubeDETR(nn.Module):
             src_fast = self._project(src_fast_feat)
         src = self._project(src)
         n, f, h, w = src.shape
-        n_clips = math.ceil(t / k)
-        assert n == b * n_clips, "all videos of a batch must have the same number of slow clips"
+        Fk.check_slow_count(n, lay)  # sum ceil(d / k) slow frames: any mix of clip counts
         tpad_mask_t = torch.ones(b * t, h, w, dtype=torch.bool, device=dev)
         if self.fast:
             if identity:
@@ -330,7 +345,6 @@ class TubeDETR(nn.Module):
                 fast_src = fast_rows.permute(0, 3, 1, 2)
                 tpad_mask_t[dest] = mask_fast
         else:  # frames inherit the mask of their slow clip (tubedetr.py:172-178)
-            clip_of = torch.cat([i * n_clips + torch.arange(d) // k for i, d in enumerate(durations)]).to(dev)
             tpad_mask_t[dest] = mask[clip_of]
         tpad_mask_t[:, 0, 0] = False  # avoid empty masks (tpad_mask_t is this call's own tensor: a fresh one or a clone)
         return VideoFeatures(src, mask, pos[-1] if want_pos else None, fast_src, tpad_mask_t, durations, k)
