@@ -610,6 +610,76 @@ typedef struct td_replica_maps_out {
 } td_replica_maps_out;
 int td_replica_maps(const int* table, int b, int t, int k, int hw, int L, int n_clips, const td_replica_maps_out* out, td_stream_t stream);
 
+/* ---- Grounded tubes drawn into decoded frames (an addition WITHIN ABI 11: nothing above changed) -----------------------
+ * Writes the answer to a grounding question - the box of every frame, the temporal span, the decoder's attention - into the
+ * decoded frames of many clips in ONE launch, in the frames' own pixel format (the reference's demo re-opens every frame
+ * as a JPEG in matplotlib: demo_stvg.py:152-194, server_stvg.py:218-257).  Per job:
+ *   T frames of sh x sw in fmt = TD_SRC_RGB24 / TD_SRC_I420 / TD_SRC_NV12, planes, pitches and frame stride described as in
+ *   td_resample_src_job (odd sizes are legal, chroma planes are (sh + 1) / 2 x (sw + 1) / 2), once for the source (src0..2)
+ *   and once for the destination (dst0..2).  A destination plane may BE its source plane (same pointer, pitch and frame
+ *   stride: in place); any other overlap of a destination plane with a source plane is an error.  Every byte of the rows of
+ *   the job's destination frames gets the value defined below; no other byte is written (not the row padding between the row
+ *   and the pitch), and no byte outside the source rows is read.
+ * Inputs, device pointers, each nullable (NULL leaves its layer out):
+ *   boxes      fp32 [n_tube][4], xyxy in source pixels (what PostProcess returns);
+ *   span       int64 [2]: first and last tube row that contain the object, both inclusive (one row of td_sted_decode's
+ *              output); NULL: every row does;
+ *   frame_map  int32 [T]: the tube row r of frame t; NULL: r = t.  A frame whose r is outside [0, n_tube) is a plain copy;
+ *   heat       uint8 [n_tube][mh][mw]: one attention map per tube row;
+ *   box_color, heat_color, dim_color: three bytes IN THE FRAME'S OWN COLOUR SPACE (R, G, B or Y, U, V);
+ *   thickness >= 1 (with boxes), heat_alpha and dim_alpha in [0, 256].
+ * The rule (exact integers, reproducible to the bit).  A frame is a stack of up to three layers; a layer gives every luma
+ * pixel (rgb24: every pixel) an alpha a in [0, 256] and a colour c, and a byte v becomes (v (256 - a) + c a + 128) >> 8.
+ * In this order:
+ *   1. dim, only when span is given and r lies outside it: a = dim_alpha everywhere, c = dim_color.
+ *   2. heat, whenever heat is given: pixel (y, x) samples map r at gy = clamp(((2 y + 1) mh 128) / sh - 128, 0, 256 (mh - 1)),
+ *      gx alike from x, mw, sw (integer division of a non-negative operand); i = g >> 8, f = g & 255, neighbour min(i + 1, n - 1);
+ *      h = ((256 - fy) ((256 - fx) q00 + fx q01) + fy ((256 - fx) q10 + fx q11) + 32768) >> 16; a = (h heat_alpha + 127) / 255,
+ *      c = heat_color.
+ *   3. box, only when boxes is given and r lies inside the span: x0 = (int)floorf(bx0 + 0.5f), y0, x1, y1 alike, in fp32,
+ *      finite values clamped to +-2^20 before the conversion; a box with a non-finite coordinate or with x1 <= x0 or y1 <= y0
+ *      draws nothing.  a = 256 for a pixel in [x0, x1) x [y0, y1) that is not in [x0 + th, x1 - th) x [y0 + th, y1 - th),
+ *      c = box_color; the parts of the outline outside the frame are simply absent.
+ * A chroma sample (I420 / NV12) takes, per layer, the mean alpha of the luma pixels of its 2 x 2 block that exist,
+ * (sum + n / 2) / n with n in {1, 2, 4}, and is blended with the U / V byte of the colour (NV12: both bytes of the pair).
+ * Colours: tubedetr_amd.render.color_in_space makes the three bytes from an RGB colour by the forward of the conversion
+ * above (exact integers): Y = clamp((yr R + yg G + yb B + 2^20 yo + 2^19) >> 20), U = clamp((ur R + ug G + ub B +
+ * 2^20 128 + 2^19) >> 20), V alike (>> = floor division), coefficients round(2^20 x) of yr = Kr s_y, yg = Kg s_y,
+ * yb = Kb s_y, ur = -Kr / (2 (1 - Kb)) s_c, ug = -Kg / (2 (1 - Kb)) s_c, ub = s_c / 2, vr = s_c / 2, vg = -Kg / (2 (1 - Kr)) s_c,
+ * vb = -Kb / (2 (1 - Kr)) s_c, with s_y = 219 / 255, s_c = 224 / 255 for limited range and s_y = s_c = 1 for full range
+ * (BT.601: Kr = 0.299, Kb = 0.114; BT.709: Kr = 0.2126, Kb = 0.0722): within 0.5004 of a level of the float64 formula
+ * for every (R, G, B).  (20 fraction bits where the device rule above has 16: at 16 the three limited-range U coefficients
+ * all round the same way and bright colours come out 0.5036 off; three bytes per job are converted on the host.)
+ * Limits: sides 1..16384, mh and mw 1..256.  A violation returns an error whose message names the field; nothing is
+ * launched.  `jobs` is a host array consumed before the call returns; the job table lives in caller-provided memory as
+ * for td_clip_resample (table_host page-locked, table_dev device memory, both of td_tube_overlay_table_bytes(n_jobs)
+ * bytes).  No allocation, no synchronisation inside. */
+typedef struct td_overlay_job {
+  const void* src0; /* rgb24 pixels, or Y */
+  const void* src1; /* I420: U; NV12: UV pairs; RGB24: ignored */
+  const void* src2; /* I420: V; else ignored */
+  long long src_frame_stride;
+  int src_pitch0, src_pitch1, src_pitch2;
+  void* dst0;
+  void* dst1;
+  void* dst2;
+  long long dst_frame_stride;
+  int dst_pitch0, dst_pitch1, dst_pitch2;
+  int fmt;
+  int T, sh, sw;
+  const float* boxes;
+  const long long* span;
+  const int* frame_map;
+  const unsigned char* heat;
+  int n_tube;
+  int mh, mw;
+  int thickness;
+  int heat_alpha, dim_alpha;
+  unsigned char box_color[3], heat_color[3], dim_color[3];
+} td_overlay_job;
+size_t td_tube_overlay_table_bytes(int n_jobs);
+int td_tube_overlay(const td_overlay_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

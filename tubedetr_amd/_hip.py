@@ -67,6 +67,14 @@ class ResampleSrcJob(C.Structure):
                [("dst", C.c_void_p)] + [(n, C.c_int) for n in ("planar", "frame_off", "H", "W")] + [("mask", C.c_void_p)]
 
 
+class OverlayJob(C.Structure):
+    """td_overlay_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("src0", "src1", "src2")] + [("src_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("src_pitch0", "src_pitch1", "src_pitch2")] + \
+               [(n, C.c_void_p) for n in ("dst0", "dst1", "dst2")] + [("dst_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("dst_pitch0", "dst_pitch1", "dst_pitch2")] + \
+               [(n, C.c_int) for n in ("fmt", "T", "sh", "sw")] + [(n, C.c_void_p) for n in ("boxes", "span", "frame_map", "heat")] + \
+               [(n, C.c_int) for n in ("n_tube", "mh", "mw", "thickness", "heat_alpha", "dim_alpha")] + [(n, C.c_ubyte * 3) for n in ("box_color", "heat_color", "dim_color")]
+
+
 class ReplicaMapsOut(C.Structure):
     """td_replica_maps_out."""
     _fields_ = [(n, C.c_void_p) for n in ("owner", "vid_of_frame", "vid_of_clip", "query_mask", "frame_dest", "clip_of", "vis_src", "vis_dst", "txt_src", "txt_dst",
@@ -146,6 +154,7 @@ _SIGS = {
     "td_clip_resample": [C.POINTER(ResampleJob), _I, _P, _P, _SZ, _P],
     "td_clip_resample_src": [C.POINTER(ResampleSrcJob), _I, _P, _P, _SZ, _P],
     "td_replica_maps": [_P, _I, _I, _I, _I, _I, _I, C.POINTER(ReplicaMapsOut), _P],
+    "td_tube_overlay": [C.POINTER(OverlayJob), _I, _P, _P, _SZ, _P],
 }
 _SIZE_SIGS = {
     "td_grad_norm_ws_bytes": [],
@@ -153,6 +162,7 @@ _SIZE_SIGS = {
     "td_conv_wgrad_batch_table_bytes": [_I],
     "td_clip_resample_table_bytes": [_I],
     "td_clip_resample_src_table_bytes": [_I],
+    "td_tube_overlay_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],

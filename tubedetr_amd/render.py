@@ -1,0 +1,320 @@
+"""Grounded tubes drawn into decoded frames on the device (td_tube_overlay, csrc/overlay.hip).
+
+The reference shows an answer on the host: demo_stvg.py:152-194 and server_stvg.py:218-257 re-decode the video to JPEGs,
+open every frame in matplotlib, draw one rectangle and save the JPEG again.  Here the decoded frames stay on the device in
+the decoder's own pixel format (``DeviceFrames``); ``annotate`` writes the boxes ``PostProcess`` returned, the span
+``sted_decode`` returned and - optionally - the decoder's cross-attention (``heat_from_attention``) into them in ONE launch
+for any number of clips, and the result goes to an encoder pipe as it is.  The pixel rule is exact integer arithmetic and is
+stated in include/tubedetr_hip.h; so is the colour conversion of ``color_in_space``.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple, Union
+
+import torch
+
+from .augment import _MATRICES, _PIX_FMTS, DecodedClip
+
+MAX_SIDE = 16384
+MAX_MAP = 256
+_ONE = 1 << 20  # fixed-point one of color_in_space
+
+
+def _rgb3(name: str, c) -> Tuple[int, int, int]:
+    c = tuple(c)
+    if len(c) != 3 or any(int(v) != v or not 0 <= v <= 255 for v in c):
+        raise ValueError(f"{name} {c!r}: three integers in 0..255")
+    return tuple(int(v) for v in c)
+
+
+def _alpha(name: str, a) -> int:
+    if int(a) != a or not 0 <= a <= 256:
+        raise ValueError(f"{name} {a!r}: an integer in [0, 256]")
+    return int(a)
+
+
+@dataclass(frozen=True)
+class TubeStyle:
+    """How an answer is drawn; colours are RGB whatever the frames' pixel format (``annotate`` converts them).  The
+    defaults are the reference demo's: a #FAFF00 outline, no attention overlay, frames outside the span left as they are."""
+    box_color: Tuple[int, int, int] = (0xFA, 0xFF, 0x00)
+    thickness: int = 2
+    heat_color: Tuple[int, int, int] = (255, 0, 0)
+    heat_alpha: int = 0       # of 256, at an attention level of 255
+    dim_color: Tuple[int, int, int] = (0, 0, 0)
+    dim_alpha: int = 0        # of 256, on the frames outside the span
+
+    def __post_init__(self):
+        for n in ("box_color", "heat_color", "dim_color"):
+            object.__setattr__(self, n, _rgb3(n, getattr(self, n)))
+        for n in ("heat_alpha", "dim_alpha"):
+            object.__setattr__(self, n, _alpha(n, getattr(self, n)))
+        if int(self.thickness) != self.thickness or self.thickness < 1:
+            raise ValueError(f"thickness {self.thickness!r}: an integer >= 1")
+
+
+def _forward_coefficients(matrix: str, full_range: bool):
+    kr, kb = (0.299, 0.114) if matrix == "bt601" else (0.2126, 0.0722)
+    kg = 1.0 - kr - kb
+    sy, sc = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+    rows = ((kr * sy, kg * sy, kb * sy),
+            (-kr / (2 * (1 - kb)) * sc, -kg / (2 * (1 - kb)) * sc, 0.5 * sc),
+            (0.5 * sc, -kg / (2 * (1 - kr)) * sc, -kb / (2 * (1 - kr)) * sc))
+    return rows, (0 if full_range else 16, 128, 128)
+
+
+def color_in_space(rgb, pix_fmt: str = "rgb24", matrix: str = "bt601", full_range: bool = False) -> Tuple[int, int, int]:
+    """The three bytes a job needs for the RGB colour ``rgb``: itself for rgb24; (Y, U, V) for yuv420p / nv12, by the exact
+    integer forward of the header's conversion: component = clamp((c_r R + c_g G + c_b B + 2^20 offset + 2^19) >> 20) with
+    round(2^20 x) coefficients of the textbook matrix (include/tubedetr_hip.h lists them by Kr, Kb and the range).  Within
+    0.5004 of a level of the float64 formula for every (R, G, B).  20 fraction bits, not the 16 of the device's yuv -> rgb
+    rule: the three limited-range U coefficients all round the same way at 16 bits, which puts bright colours 0.5036 off."""
+    r, g, b = _rgb3("rgb", rgb)
+    if pix_fmt not in _PIX_FMTS:
+        raise ValueError(f"pix_fmt {pix_fmt!r}: one of {_PIX_FMTS}")
+    if pix_fmt == "rgb24":
+        return r, g, b
+    if matrix not in _MATRICES:
+        raise ValueError(f"matrix {matrix!r}: one of {_MATRICES}")
+    rows, offs = _forward_coefficients(matrix, bool(full_range))
+    out = []
+    for (cr, cg, cb), off in zip(rows, offs):
+        acc = round(_ONE * cr) * r + round(_ONE * cg) * g + round(_ONE * cb) * b + _ONE * off + _ONE // 2
+        out.append(min(max(acc >> 20, 0), 255))
+    return tuple(out)
+
+
+def heat_from_attention(ca_weights: torch.Tensor, hw: Tuple[int, int], n_valid: Optional[int] = None) -> torch.Tensor:
+    """The decoder's cross-attention ``ca_weights`` (frames, 1, S) -> uint8 [frames][h][w] maps for ``annotate``: the first
+    h w entries of a frame (its visual tokens; S = h w + text tokens) divided by the frame's largest, times 255, rounded.
+    The text tokens' share of the attention is dropped, so a map says WHERE the query looked, not how much of its attention
+    went to the picture.  ``n_valid``: use only the first n_valid frames.  Torch ops on the device, no host copy."""
+    h, w = int(hw[0]), int(hw[1])
+    if not (1 <= h <= MAX_MAP and 1 <= w <= MAX_MAP):
+        raise ValueError(f"token grid {h} x {w}: sides in 1..{MAX_MAP}")
+    if ca_weights.dim() != 3 or ca_weights.shape[1] != 1 or ca_weights.shape[2] < h * w:
+        raise ValueError(f"ca_weights {tuple(ca_weights.shape)}: (frames, 1, S) with S >= {h * w}")
+    a = ca_weights[: n_valid if n_valid is not None else ca_weights.shape[0], 0, : h * w].float()
+    top = a.amax(dim=1, keepdim=True).clamp_min(torch.finfo(torch.float32).tiny)
+    return (a / top * 255.0 + 0.5).floor().clamp_(0, 255).to(torch.uint8).view(-1, h, w)
+
+
+def _frame_bytes(pix_fmt: str, h: int, w: int) -> int:
+    if pix_fmt == "rgb24":
+        return 3 * w * h
+    return w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
+
+
+def _check_geometry(pix_fmt: str, T: int, h: int, w: int):
+    if pix_fmt not in _PIX_FMTS:
+        raise ValueError(f"pix_fmt {pix_fmt!r}: one of {_PIX_FMTS}")
+    if T < 0:
+        raise ValueError(f"T = {T} is negative")
+    if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError(f"frame size {h} x {w}: sides in 1..{MAX_SIDE}")
+
+
+@dataclass
+class DeviceFrames:
+    """T decoded frames of h x w ON THE DEVICE, laid out as ``DecodedClip`` lays them out on the host: ``data`` is the flat
+    uint8 tensor, tightly packed, frame after frame (yuv420p: Y, U, V; nv12: Y, UV; rgb24: (h, w, 3))."""
+    data: torch.Tensor
+    T: int
+    h: int
+    w: int
+    pix_fmt: str = "yuv420p"
+    matrix: str = "bt601"
+    full_range: bool = False
+
+    def __post_init__(self):
+        self.T, self.h, self.w = int(self.T), int(self.h), int(self.w)
+        _check_geometry(self.pix_fmt, self.T, self.h, self.w)
+        if self.matrix not in _MATRICES:
+            raise ValueError(f"matrix {self.matrix!r}: one of {_MATRICES}")
+        d = self.data
+        if not torch.is_tensor(d) or d.dtype != torch.uint8 or not d.is_cuda or not d.is_contiguous():
+            raise ValueError("data is a contiguous uint8 tensor on the device")
+        if d.numel() != self.T * self.nbytes_per_frame:
+            raise ValueError(f"{d.numel()} bytes for {self.T} {self.pix_fmt} frames of {self.h} x {self.w} ({self.nbytes_per_frame} bytes each)")
+        self.data = d.view(-1)
+
+    @property
+    def nbytes_per_frame(self) -> int:
+        return _frame_bytes(self.pix_fmt, self.h, self.w)
+
+    @classmethod
+    def from_decoded(cls, clip: DecodedClip, device) -> "DeviceFrames":
+        """One upload of a ``DecodedClip`` through page-locked memory (asynchronous on the current stream)."""
+        host = clip.data if clip.data.is_pinned() else clip.data.pin_memory()
+        return cls(host.to(device, non_blocking=True), clip.T, clip.h, clip.w, clip.pix_fmt, clip.matrix, clip.full_range)
+
+    def empty_like(self) -> "DeviceFrames":
+        return DeviceFrames(torch.empty_like(self.data), self.T, self.h, self.w, self.pix_fmt, self.matrix, self.full_range)
+
+
+def _planes(pix_fmt: str, sh: int, sw: int):
+    """(fmt code, tight pitches, plane sizes) of one frame."""
+    from . import _hip
+
+    ch, cw = (sh + 1) // 2, (sw + 1) // 2
+    if pix_fmt == "rgb24":
+        return _hip.TD_SRC_RGB24, [3 * sw], [3 * sw * sh]
+    if pix_fmt == "yuv420p":
+        return _hip.TD_SRC_I420, [sw, cw, cw], [sw * sh, cw * ch, cw * ch]
+    return _hip.TD_SRC_NV12, [sw, 2 * cw], [sw * sh, 2 * cw * ch]
+
+
+def _describe(base, sizes, tight, planes, pitches, frame_stride):
+    pitches = list(tight if pitches is None else pitches)
+    if planes is None:
+        planes = [base + sum(sizes[:i]) for i in range(len(sizes))]
+        if frame_stride is None:
+            frame_stride = sum(sizes)
+    if len(planes) != len(sizes) or len(pitches) != len(sizes) or frame_stride is None:
+        raise ValueError("one address and one pitch per plane, and the frame stride")
+    return list(planes) + [None] * (3 - len(sizes)), pitches + [0] * (3 - len(sizes)), int(frame_stride)
+
+
+def overlay_job(src: int, T: int, sh: int, sw: int, dst: Optional[int] = None, pix_fmt: str = "rgb24", boxes: Optional[int] = None, n_tube: int = 0,
+                span: Optional[int] = None, frame_map: Optional[int] = None, heat: Optional[int] = None, heat_hw: Tuple[int, int] = (0, 0),
+                box_color=(0xFA, 0xFF, 0x00), heat_color=(255, 0, 0), dim_color=(0, 0, 0), thickness: int = 2, heat_alpha: int = 0, dim_alpha: int = 0,
+                src_planes: Optional[Sequence[int]] = None, src_pitches: Optional[Sequence[int]] = None, src_frame_stride: Optional[int] = None,
+                dst_planes: Optional[Sequence[int]] = None, dst_pitches: Optional[Sequence[int]] = None, dst_frame_stride: Optional[int] = None):
+    """One ``td_overlay_job``: T frames of sh x sw in ``pix_fmt`` at device address ``src``, annotated into ``dst`` (None:
+    in place).  ``boxes`` / ``span`` / ``frame_map`` / ``heat`` are device addresses or None (fp32 [n_tube][4], int64 [2],
+    int32 [T], uint8 [n_tube][heat_hw[0]][heat_hw[1]]); the colours are three bytes in the FRAMES' colour space
+    (``color_in_space``).  Without ``*_planes`` / ``*_pitches`` / ``*_frame_stride`` the frames are tightly packed
+    (``DeviceFrames``); else the planes are the device addresses of frame 0's planes and the pitches their row pitches."""
+    from . import _hip
+
+    T, sh, sw = int(T), int(sh), int(sw)
+    _check_geometry(pix_fmt, T, sh, sw)
+    if int(thickness) != thickness or thickness < 1:
+        raise ValueError(f"thickness {thickness!r}: an integer >= 1")
+    mh, mw = int(heat_hw[0]), int(heat_hw[1])
+    if heat is not None and not (1 <= mh <= MAX_MAP and 1 <= mw <= MAX_MAP):
+        raise ValueError(f"token grid {mh} x {mw}: sides in 1..{MAX_MAP}")
+    if n_tube < 0:
+        raise ValueError(f"n_tube = {n_tube} is negative")
+    fmt, tight, sizes = _planes(pix_fmt, sh, sw)
+    j = _hip.OverlayJob()
+    (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride = _describe(src, sizes, tight, src_planes, src_pitches, src_frame_stride)
+    if dst is None and dst_planes is None:
+        (j.dst0, j.dst1, j.dst2), (j.dst_pitch0, j.dst_pitch1, j.dst_pitch2), j.dst_frame_stride = (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride
+    else:
+        (j.dst0, j.dst1, j.dst2), (j.dst_pitch0, j.dst_pitch1, j.dst_pitch2), j.dst_frame_stride = _describe(dst, sizes, tight, dst_planes, dst_pitches, dst_frame_stride)
+    j.fmt, j.T, j.sh, j.sw = fmt, T, sh, sw
+    j.boxes, j.span, j.frame_map, j.heat = boxes, span, frame_map, heat
+    j.n_tube, j.mh, j.mw = int(n_tube), mh, mw
+    j.thickness, j.heat_alpha, j.dim_alpha = int(thickness), _alpha("heat_alpha", heat_alpha), _alpha("dim_alpha", dim_alpha)
+    j.box_color[:], j.heat_color[:], j.dim_color[:] = _rgb3("box_color", box_color), _rgb3("heat_color", heat_color), _rgb3("dim_color", dim_color)
+    return j
+
+
+def tube_overlay(jobs: Sequence, device) -> tuple:
+    """One td_tube_overlay launch on the current stream with freshly allocated job tables; returns them: the caller keeps
+    them alive until the stream has passed the launch (``annotate`` recycles its own instead)."""
+    from . import _hip
+
+    lib = _hip.lib()
+    nb = int(lib.td_tube_overlay_table_bytes(len(jobs)))
+    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
+    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
+    arr = (_hip.OverlayJob * len(jobs))(*jobs)
+    _hip.check(lib.td_tube_overlay(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_tube_overlay")
+    return host, dev
+
+
+# job tables of annotate(): (pinned, device, event recorded behind the launch).  A table is taken again only once its event has
+# completed (a query, never a wait); otherwise a new one is made, so the pool grows to the number of launches in flight.
+_tables: List[tuple] = []
+
+
+def _take_table(nb: int, device):
+    for i, (host, dev, ev) in enumerate(_tables):
+        if host.numel() >= nb and dev.device == device and ev.query():
+            return _tables.pop(i)
+    n = max(nb, 4096)
+    return torch.empty(n, dtype=torch.uint8, pin_memory=True), torch.empty(n, dtype=torch.uint8, device=device), torch.cuda.Event()
+
+
+def _as_list(v, n: int, name: str):
+    if v is None:
+        return [None] * n
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError(f"{name}: {len(v)} entries for {n} clips")
+        return list(v)
+    if n != 1:
+        raise ValueError(f"{name}: a list with one entry per clip")
+    return [v]
+
+
+def _dev_tensor(t, dtype, shape_tail, name, device):
+    if t is None:
+        return None
+    ok = torch.is_tensor(t) and t.device == device and t.dtype == dtype
+    if ok and shape_tail:
+        ok = t.dim() >= len(shape_tail) and tuple(t.shape[t.dim() - len(shape_tail):]) == tuple(shape_tail)
+    if not ok:
+        raise ValueError(f"{name}: a {dtype} tensor [..., {', '.join(map(str, shape_tail))}] on {device}")
+    return t.contiguous()
+
+
+def annotate(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=None, heat=None, frame_map=None, style: TubeStyle = TubeStyle(),
+             out: Union[None, DeviceFrames, Sequence[DeviceFrames]] = None):
+    """Draw grounded tubes into decoded frames: ONE launch for one clip or for a list of clips (then ``boxes``, ``span``,
+    ``heat``, ``frame_map`` and ``out`` are lists too, or None).  Per clip:
+      boxes      fp32 (n_tube, 4) xyxy in the frames' pixels on the device: what ``PostProcess`` returned for the clip, stacked; None: no box;
+      span       int64 (2,): the clip's row of ``sted_decode``'s output (first and last tube row with the object); None: all rows;
+      heat       uint8 (n_tube, mh, mw) from ``heat_from_attention``; None: no attention overlay;
+      frame_map  int32 (T,): the tube row of each frame (a clip decoded at full rate, a tube predicted at 5 fps); None: frame t is row t;
+      out        ``DeviceFrames`` of the same geometry to write into; the clip itself: in place; None: a new buffer.
+    Returns the annotated ``DeviceFrames`` (a list for a list).  Nothing here synchronises or copies to the host; ``style``'s
+    RGB colours are converted to the frames' colour space by ``color_in_space``."""
+    from . import _hip
+
+    single = isinstance(frames, DeviceFrames)
+    clips = [frames] if single else list(frames)
+    n = len(clips)
+    if n == 0:
+        return []
+    device = clips[0].data.device
+    boxes_l, span_l, heat_l, map_l, out_l = (_as_list(v, n, k) for v, k in ((boxes, "boxes"), (span, "span"), (heat, "heat"), (frame_map, "frame_map"), (out, "out")))
+    jobs, keep, results = [], [], []
+    for c, b, s, h, m, o in zip(clips, boxes_l, span_l, heat_l, map_l, out_l):
+        if not isinstance(c, DeviceFrames) or c.data.device != device:
+            raise ValueError("frames: DeviceFrames on one device")
+        b = _dev_tensor(b, torch.float32, (4,), "boxes", device)
+        s = _dev_tensor(s, torch.int64, (2,), "span", device)
+        h = _dev_tensor(h, torch.uint8, (), "heat", device)
+        m = _dev_tensor(m, torch.int32, (c.T,), "frame_map", device)
+        if b is not None and b.dim() != 2 or s is not None and s.dim() != 1 or m is not None and m.dim() != 1 or h is not None and h.dim() != 3:
+            raise ValueError("boxes (n_tube, 4), span (2,), heat (n_tube, mh, mw), frame_map (T,)")
+        if b is not None and h is not None and b.shape[0] != h.shape[0]:
+            raise ValueError(f"boxes have {b.shape[0]} tube rows, heat has {h.shape[0]}")
+        n_tube = b.shape[0] if b is not None else h.shape[0] if h is not None else 2 ** 31 - 1  # span only: no array that a row could index past
+        if o is None:
+            o = c.empty_like()
+        elif not isinstance(o, DeviceFrames) or (o.T, o.h, o.w, o.pix_fmt) != (c.T, c.h, c.w, c.pix_fmt) or o.data.device != device:
+            raise ValueError("out: DeviceFrames of the clip's geometry and pixel format on its device")
+        space = (c.pix_fmt, c.matrix, c.full_range)
+        jobs.append(overlay_job(c.data.data_ptr(), c.T, c.h, c.w, o.data.data_ptr(), c.pix_fmt, _hip.ptr(b), n_tube, _hip.ptr(s), _hip.ptr(m), _hip.ptr(h),
+                                tuple(h.shape[1:]) if h is not None else (0, 0), color_in_space(style.box_color, *space), color_in_space(style.heat_color, *space),
+                                color_in_space(style.dim_color, *space), style.thickness, style.heat_alpha, style.dim_alpha))
+        keep.append((b, s, h, m))
+        results.append(o)
+    lib = _hip.lib()
+    nb = int(lib.td_tube_overlay_table_bytes(n))
+    host, dev, ev = _take_table(nb, device)
+    arr = (_hip.OverlayJob * n)(*jobs)
+    _hip.check(lib.td_tube_overlay(arr, n, host.data_ptr(), dev.data_ptr(), host.numel(), _hip.stream_ptr()), "td_tube_overlay")
+    ev.record()
+    _tables.append((host, dev, ev))
+    stream = torch.cuda.current_stream(device)
+    for group in keep:  # contiguous() may have made copies: the allocator must not hand them out before the launch has run
+        for t in group:
+            if t is not None:
+                t.record_stream(stream)
+    return results[0] if single else results
