@@ -205,8 +205,10 @@ extern "C" int td_criterion_fwd(const float* boxes, const float* tgt, const long
                                 const uint8_t* time_mask, const uint8_t* positive, const int* inter, const float* num_boxes_dev,
                                 float num_boxes_host, float sigma, int nl, int b, int T, int n, float* losses, float* g_l1, float* g_giou,
                                 float* g_sted, float* g_w, td_stream_t stream) {
-  TD_REQUIRE(boxes && tgt && keep && losses && g_l1 && g_giou, "td_criterion_fwd: null pointer");
+  TD_REQUIRE(boxes && losses && g_l1 && g_giou, "td_criterion_fwd: null pointer");
   TD_REQUIRE(nl >= 1 && b >= 1 && T >= 1 && n >= 0, "td_criterion_fwd: bad sizes");
+  // a batch without any annotated frame: empty tensors have no storage, and the loop over n never reads keep / tgt
+  TD_REQUIRE(n == 0 || (tgt && keep), "td_criterion_fwd: null keep / tgt with n=%d annotated frames", n);
   TD_REQUIRE(!sted || (time_mask && inter && g_sted), "td_criterion_fwd: pred_sted needs time_mask, inter and g_sted");
   TD_REQUIRE(!weights || (time_mask && positive && g_w), "td_criterion_fwd: weights need time_mask, positive and g_w");
   TD_REQUIRE(sigma > 0.f, "td_criterion_fwd: sigma must be positive");

@@ -415,9 +415,28 @@ class CriterionFn(torch.autograd.Function):
     def forward(ctx, boxes, sted, weights, tgt, keep, tm_u8, pm_u8, inter_dev, num_boxes, sigma):
         from .. import _hip
 
-        nl, bt, _ = boxes.shape
+        # the kernel reads raw pointers: refuse what it would misread (dtypes and shapes are host metadata, no device sync)
+        for name, x in (("boxes", boxes), ("sted", sted), ("weights", weights)):
+            if x is not None and x.dtype != torch.float32:
+                raise TypeError(f"CriterionFn: {name} must be float32, got {x.dtype}")
+        if keep.dtype != torch.int64:
+            raise TypeError(f"CriterionFn: keep must be int64, got {keep.dtype}")
+        if tm_u8.dtype != torch.uint8 or pm_u8.dtype != torch.uint8 or inter_dev.dtype != torch.int32:
+            raise TypeError(f"CriterionFn: time_mask / positive_map must be uint8 and inter_idx int32, got {tm_u8.dtype}, {pm_u8.dtype}, {inter_dev.dtype}")
+        if tm_u8.dim() != 2 or tuple(pm_u8.shape) != tuple(tm_u8.shape) or tuple(inter_dev.shape) != (tm_u8.shape[0], 2):
+            raise ValueError(f"CriterionFn: time_mask {tuple(tm_u8.shape)}, positive_map {tuple(pm_u8.shape)} and inter_idx {tuple(inter_dev.shape)} disagree")
         b, T = tm_u8.shape
+        if boxes.dim() != 3 or boxes.shape[1] != b * T or boxes.shape[2] != 4:
+            raise ValueError(f"CriterionFn: boxes must be [layers, b*T = {b * T}, 4] for a time_mask of {(b, T)}, got {tuple(boxes.shape)}")
+        nl = boxes.shape[0]
+        if sted is not None and tuple(sted.shape) != (nl, b, T, 2):
+            raise ValueError(f"CriterionFn: sted must be {(nl, b, T, 2)}, got {tuple(sted.shape)}")
+        if weights is not None and tuple(weights.shape) != (nl, b, T, T):
+            raise ValueError(f"CriterionFn: weights must be {(nl, b, T, T)}, got {tuple(weights.shape)}")
+        if keep.dim() != 1 or tuple(tgt.shape) != (keep.numel(), 4):
+            raise ValueError(f"CriterionFn: keep must be [n] and tgt [n, 4], got {tuple(keep.shape)} and {tuple(tgt.shape)}")
         dev = boxes.device
+        keep, tm_u8, pm_u8, inter_dev = keep.contiguous(), tm_u8.contiguous(), pm_u8.contiguous(), inter_dev.contiguous()
         boxes, tgt = boxes.contiguous(), tgt.contiguous().float()
         sted = sted.contiguous() if sted is not None else None
         weights = weights.contiguous() if weights is not None else None
@@ -567,10 +586,12 @@ class SetCriterion(nn.Module):
         positive_map = self._positive_map(inter_idx, time_mask)
         key = ("fz", tuple(map(tuple, inter_idx)), tuple(time_mask.shape), str(dev))
         hit = self._tgt_cache.get(key)
-        if hit is None:
-            hit = self._tgt_cache[key] = (time_mask.to(torch.uint8).contiguous(), positive_map.to(torch.uint8).contiguous(),
+        if hit is None:  # only what the key determines: two batches with one key can differ in a shorter video's duration
+            hit = self._tgt_cache[key] = (positive_map.to(torch.uint8).contiguous(),
                                           torch.tensor([[int(x[0]), int(x[1])] for x in inter_idx], dtype=torch.int32).to(dev))
-        tm_u8, pm_u8, inter_dev = hit
+        pm_u8, inter_dev = hit
+        # this call's own mask: a bool tensor is one byte of 0 / 1 per element, so the view is no launch and no copy
+        tm_u8 = (time_mask if time_mask.dtype == torch.bool else time_mask != 0).contiguous().view(torch.uint8)
         L = CriterionFn.apply(boxes, sted, weights, tgt_boxes, keep, tm_u8, pm_u8, inter_dev, num_boxes, float(self.sigma))
         self.last_loss_matrix = L
         losses, self._fused_keys = {}, set()
