@@ -680,6 +680,41 @@ typedef struct td_overlay_job {
 size_t td_tube_overlay_table_bytes(int n_jobs);
 int td_tube_overlay(const td_overlay_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
 
+/* ---- Scored K-best moments (an addition WITHIN ABI 11: nothing above changed) ------------------------------------------
+ * Per video the K likeliest (start, end) pairs that are not near-copies of each other, with their log-probabilities:
+ * td_sted_decode's arg-max continued by a greedy temporal NMS, with the window ensembling of PostProcessSTVG
+ * (models/postprocessors.py:27-53) done by the kernel.  ONE launch, one workgroup per video, whatever K is; no
+ * allocation, no synchronisation, no atomics: the result does not depend on scheduling.  This comment is the rule.
+ *   steds   fp32 [n_windows][T][2] logits (start, end);
+ *   valid   bytes [n_windows][T], 0 = padded position; NULL = every position is valid;
+ *   win_ptr device int32 [n_videos + 1]: video v owns the windows win_ptr[v] .. win_ptr[v + 1] - 1; NULL = window v alone
+ *           (then n_windows >= n_videos).  The caller guarantees a non-decreasing table that ends at n_windows and gives
+ *           no video more than max_windows windows; the kernel clamps a video's window count to [0, max_windows] and
+ *           every window index to [0, n_windows), so a wrong table cannot make it read outside steds / valid.
+ * Positions.  Video v has P_v = n_w(v) T positions; position p = (w - win_ptr[v]) T + j is entry j of window w: the
+ *   reference's concatenation.  Padded slots keep their place, so p indexes the video's frames_id list.  A padded position
+ *   has logit -inf in both channels; a -inf logit in steds means the same.
+ * Score.  ls = log_softmax of the start logits over the P_v positions, le alike of the end logits, in td_sted_decode's
+ *   arithmetic order (maximum m, sum S of expf(x - m), then (x - m) - logf(S), all fp32, the sums partitioned as there, so
+ *   ls and le are td_sted_decode's bit for bit); score(s, e) = ls[s] + le[e], one fp32 addition.
+ * Picks.  For k = 0 .. K - 1 the pick is the pair of the largest score among the pairs with
+ *     s < e,  a finite score (neither -inf nor NaN),  not an earlier pick and not suppressed by an earlier pick.
+ *   Ties are exact (bit-equal fp32 scores) and go to the smallest e, then the smallest s: td_sted_decode's order, torch's.
+ * Suppression, in 64-bit integers.  For an earlier pick (a, b): inter = max(0, min(e, b) - max(s, a) + 1),
+ *   union = (e - s + 1) + (b - a + 1) - inter; (s, e) is suppressed iff inter * nms_den > nms_num * union.  A temporal IoU
+ *   exactly equal to nms_num / nms_den is kept.  nms_num == nms_den suppresses nothing but the picks themselves (plain
+ *   top-K); nms_num == 0 suppresses every pair that shares a frame with a pick.
+ * Outputs.  count[v] = number of picks made (< K when no admissible pair is left; 0 for a video of fewer than two valid
+ *   positions); pairs [n_videos][K][2] int64 and scores [n_videos][K] fp32 hold the picks in order, rows k >= count[v]
+ *   hold (-1, -1) and -inf.  Row 0 is td_sted_decode's answer whenever an admissible pair exists.
+ * Refused on the host (td_last_error, nothing launched): a null steds / pairs / scores / count; n_videos < 1, T < 1,
+ *   max_windows < 1, n_windows < 1 (without win_ptr: n_windows < n_videos); K outside 1 .. 32; nms_den < 1, nms_num < 0 or
+ *   nms_num > nms_den; max_windows * T > 3840 (the two log-probability vectors and the per-end best start of a video stay
+ *   in LDS for all K rounds: td_sted_decode's bound). */
+int td_sted_topk(const float* steds, const unsigned char* valid, const int* win_ptr, int n_videos, int n_windows, int T,
+                 int max_windows, int K, int nms_num, int nms_den, long long* pairs, float* scores, int* count,
+                 td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

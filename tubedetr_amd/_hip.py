@@ -155,6 +155,7 @@ _SIGS = {
     "td_clip_resample_src": [C.POINTER(ResampleSrcJob), _I, _P, _P, _SZ, _P],
     "td_replica_maps": [_P, _I, _I, _I, _I, _I, _I, C.POINTER(ReplicaMapsOut), _P],
     "td_tube_overlay": [C.POINTER(OverlayJob), _I, _P, _P, _SZ, _P],
+    "td_sted_topk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
 }
 _SIZE_SIGS = {
     "td_grad_norm_ws_bytes": [],
