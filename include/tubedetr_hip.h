@@ -428,14 +428,16 @@ int td_mha_lean_bwd(const void* q, const void* k, const void* v, const uint8_t* 
  * another (the flat buffer of the data-parallel exchange).  The buffers are tiled by at most TD_OPTIM_MAX_SEGMENTS
  * segments; a segment belongs to one parameter group (learning rate index: 0 = transformer + heads, 1 = backbone,
  * 2 = text encoder, main.py:381-405) and is `active` unless its parameters received no gradient (RoBERTa's pooler:
- * torch skips p.grad is None in clip_grad_norm_ and in optimizer.step()). */
+ * torch skips p.grad is None in clip_grad_norm_ and in optimizer.step()).  An inactive segment keeps param, exp_avg and
+ * exp_avg_sq bit for bit and its gradients are never read into the norm; only its EMA moves,
+ * ema = ema*ema_decay + (1-ema_decay)*param, as update_ema (util/optim.py:8-25) does for every state-dict entry. */
 #define TD_OPTIM_MAX_SEGMENTS 32
 #define TD_OPTIM_MAX_GROUPS 4
 #define TD_OPTIM_NORM_BLOCKS 2048
 typedef struct td_optim_segment {
   long long begin, end; /* element range [begin, end) */
   int group;            /* index into lr_dev[] */
-  int active;           /* 0: left untouched */
+  int active;           /* 0: no gradient - only the EMA is updated */
 } td_optim_segment;
 /* Replaces torch.nn.utils.clip_grad_norm_ (engine.py:149-150): norm_clip[0] = L2 norm of all active gradients,
  * norm_clip[1] = min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0); *step (device int, may be NULL) += 1.

@@ -89,14 +89,19 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
   if (ema) *ema = *ema * a.ema_decay + (1.f - a.ema_decay) * p;
 }
 
+// a parameter without a gradient keeps its value and its moments, but update_ema (util/optim.py:8-25) still moves its EMA
+__device__ __forceinline__ float ema_only(float e, float p, const AdamArgs& a) { return e * a.ema_decay + (1.f - a.ema_decay) * p; }
+
 __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, float* __restrict__ ema, long long n, Segs sg,
                                                         const float* __restrict__ lr_dev, const float* __restrict__ norm_clip,
                                                         const int* __restrict__ step_dev, AdamArgs a) {
   const float clip = norm_clip ? norm_clip[1] : 1.f;
   const int step = step_dev[0];  // already incremented for this update
-  const float bc1 = 1.f - powf(a.b1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(a.b2, (float)step));
+  // 1 - beta^t as -expm1(t * log(beta)): 1.f - powf(beta2, t) cancels while t is small (t = 3: 0.997 -> 0.003 carries the
+  // rounding of 0.997, 1e-5 relative in every update); beta - 1 is exact in fp32
+  const float bc1 = -expm1f((float)step * log1pf(a.b1 - 1.f));
+  const float bc2s = sqrtf(-expm1f((float)step * log1pf(a.b2 - 1.f)));
   float lrs[TD_OPTIM_MAX_GROUPS];
 #pragma unroll
   for (int q = 0; q < TD_OPTIM_MAX_GROUPS; ++q) lrs[q] = lr_dev[q];
@@ -104,14 +109,25 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, c
   for (long long vi = (long long)blockIdx.x * 256 + threadIdx.x; vi < nv; vi += (long long)gridDim.x * 256) {
     const long long i0 = vi << 2;
     const int k0 = find_seg(sg, i0), k1 = find_seg(sg, i0 + 3);
-    if (k0 == k1 && !sg.s[k0].active) continue;
+    if (k0 == k1 && !sg.s[k0].active) {
+      if (ema) {
+        const float4 P = ((const float4*)p)[vi];
+        float4 E = ((float4*)ema)[vi];
+        E.x = ema_only(E.x, P.x, a); E.y = ema_only(E.y, P.y, a); E.z = ema_only(E.z, P.z, a); E.w = ema_only(E.w, P.w, a);
+        ((float4*)ema)[vi] = E;
+      }
+      continue;
+    }
     float4 P = ((float4*)p)[vi], G = ((const float4*)g)[vi], M = ((float4*)m)[vi], V = ((float4*)v)[vi], E = make_float4(0, 0, 0, 0);
     if (ema) E = ((float4*)ema)[vi];
     float* pe = (float*)&P; float* ge = (float*)&G; float* me = (float*)&M; float* ve = (float*)&V; float* ee = (float*)&E;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int k = (k0 == k1) ? k0 : find_seg(sg, i0 + q);
-      if (!sg.s[k].active) continue;
+      if (!sg.s[k].active) {
+        if (ema) ee[q] = ema_only(ee[q], pe[q], a);
+        continue;
+      }
       adam_elem(pe[q], ge[q], me[q], ve[q], ema ? &ee[q] : nullptr, lrs[sg.s[k].group], clip, bc1, bc2s, a);
     }
     ((float4*)p)[vi] = P; ((float4*)m)[vi] = M; ((float4*)v)[vi] = V;
@@ -120,7 +136,10 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, c
   if (blockIdx.x == 0)
     for (long long i = (nv << 2) + threadIdx.x; i < n; i += 256) {
       const int k = find_seg(sg, i);
-      if (!sg.s[k].active) continue;
+      if (!sg.s[k].active) {
+        if (ema) ema[i] = ema_only(ema[i], p[i], a);
+        continue;
+      }
       adam_elem(p[i], g[i], m[i], v[i], ema ? &ema[i] : nullptr, lrs[sg.s[k].group], clip, bc1, bc2s, a);
     }
 }

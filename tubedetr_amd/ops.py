@@ -423,6 +423,12 @@ def cast(x: Tensor, dtype: torch.dtype) -> Tensor:
     return y
 
 
+def _contig(*tensors) -> None:
+    """The flat kernels below take numel() / shape and a raw pointer: a strided view would be read as if it were dense."""
+    for t in tensors:
+        assert t is None or t.is_contiguous(), "tubedetr_amd elementwise ops need contiguous tensors"
+
+
 def maxpool3x3s2(x: Tensor) -> Tensor:
     N, H, W, Cc = x.shape
     y = torch.empty((N, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), Cc), dtype=x.dtype, device=x.device)
@@ -431,6 +437,7 @@ def maxpool3x3s2(x: Tensor) -> Tensor:
 
 
 def add_layernorm_fwd(x: Tensor, r: Optional[Tensor], gamma: Tensor, beta: Tensor, eps: float, save: bool = True):
+    _contig(x, r, gamma, beta)
     rows, cols = x.shape
     y = torch.empty_like(x)
     s = torch.empty_like(x) if (save and r is not None) else None
@@ -442,6 +449,7 @@ def add_layernorm_fwd(x: Tensor, r: Optional[Tensor], gamma: Tensor, beta: Tenso
 
 
 def add_layernorm_bwd(dy: Tensor, s: Tensor, mean: Tensor, rstd: Tensor, gamma: Tensor, extra: Optional[Tensor] = None):
+    _contig(dy, s, mean, rstd, gamma, extra)
     rows, cols = dy.shape
     ds = torch.empty_like(dy)
     dgamma = zeros_f32(cols, dy.device)
@@ -452,6 +460,7 @@ def add_layernorm_bwd(dy: Tensor, s: Tensor, mean: Tensor, rstd: Tensor, gamma: 
 
 
 def colsum(g: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    _contig(g, out)
     rows, cols = g.shape
     o = out if out is not None else zeros_f32(cols, g.device)
     check(_hip.lib().td_colsum(ptr(g), ptr(o), rows, cols, cols, dtype_code(g.dtype), stream_ptr()), "td_colsum")
@@ -459,12 +468,14 @@ def colsum(g: Tensor, out: Optional[Tensor] = None) -> Tensor:
 
 
 def add(a: Tensor, b: Optional[Tensor]) -> Tensor:
+    _contig(a, b)
     y = torch.empty_like(a)
     check(_hip.lib().td_add(ptr(a), ptr(b), ptr(y), a.numel(), dtype_code(a.dtype), stream_ptr()), "td_add")
     return y
 
 
 def relu_bwd(dy: Tensor, y: Tensor, scale: float = 1.0) -> Tensor:
+    _contig(dy, y)
     g = torch.empty_like(dy)
     check(_hip.lib().td_relu_bwd(ptr(dy), ptr(y), ptr(g), dy.numel(), scale, dtype_code(dy.dtype), stream_ptr()), "td_relu_bwd")
     return g
@@ -638,18 +649,21 @@ def mha_bwd(q: Tensor, k: Tensor, v: Tensor, dout: Tensor, probs: Tensor, dwavg:
 
 
 def gelu_fwd(x: Tensor) -> Tensor:
+    _contig(x)
     y = torch.empty_like(x)
     check(_hip.lib().td_gelu_fwd(ptr(x), ptr(y), x.numel(), dtype_code(x.dtype), stream_ptr()), "td_gelu_fwd")
     return y
 
 
 def gelu_bwd(dy: Tensor, x: Tensor) -> Tensor:
+    _contig(dy, x)
     dx = torch.empty_like(dy)
     check(_hip.lib().td_gelu_bwd(ptr(dy), ptr(x), ptr(dx), dy.numel(), dtype_code(dy.dtype), stream_ptr()), "td_gelu_bwd")
     return dx
 
 
 def dropout(x: Tensor, p: float, seed: int) -> Tensor:
+    _contig(x)
     y = torch.empty_like(x)
     check(_hip.lib().td_dropout(ptr(x), ptr(y), x.numel(), p, seed & 0xFFFFFFFF, _ctr() if p > 0 else None, dtype_code(x.dtype), stream_ptr()),
           "td_dropout")

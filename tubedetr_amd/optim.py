@@ -151,8 +151,10 @@ class FusedAdamWEMA:
 
     @torch.no_grad()
     def step(self):
-        """clip_grad_norm_ + AdamW.step + update_ema.  Parameters whose ``.grad`` is None are left untouched, like torch
-        does; which ones those are must not change between steps (it is a property of the model: RoBERTa's pooler)."""
+        """clip_grad_norm_ + AdamW.step + update_ema.  Parameters whose ``.grad`` is None keep their value and moments, like
+        torch leaves them, and stay out of the norm; their EMA still moves towards them, as update_ema moves every entry
+        (it matters once ``ema_model`` was loaded separately).  A change of which parameters those are rebuilds the segments;
+        there is one step counter, so a parameter that starts late gets the global t in its bias corrections (torch: its own)."""
         grads = [p.grad for p in self.params]
         active = [g is not None for g in grads]
         if active != self._active:
