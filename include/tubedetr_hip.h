@@ -717,6 +717,73 @@ int td_sted_topk(const float* steds, const unsigned char* valid, const int* win_
                  int max_windows, int K, int nms_num, int nms_den, long long* pairs, float* scores, int* count,
                  td_stream_t stream);
 
+/* ---- Grounded tubes cropped out of decoded frames (an addition WITHIN ABI 11: nothing above changed) -------------------
+ * Takes the object's pixels out of the decoded frames of many clips in ONE launch: per frame the window around the tube's
+ * box, resized to a fixed oh x ow - a thumbnail strip, the input of a second-stage model, a mined track.  It is
+ * td_clip_resample with the window read on the device, per frame, from the box: no boxes.cpu(), no per-frame job records.
+ * Per job:
+ *   Source.  T frames of sh x sw in fmt = TD_SRC_RGB24 / TD_SRC_I420 / TD_SRC_NV12: plane0..2, frame_stride, pitch0..2,
+ *     matrix, full_range exactly as in td_resample_src_job (odd sizes are legal, chroma planes are (sh + 1) / 2 x (sw + 1) / 2).
+ *   Tube.  Device pointers boxes (fp32 [n_tube][4], xyxy in source pixels, required), span (int64 [2], nullable) and
+ *     frame_map (int32 [T], nullable), and n_tube: what they are in td_overlay_job.
+ *   Geometry.  oh x ow: the output size; margin_num / margin_den: context added on every side as a fraction of the box
+ *     side; keep_aspect 0 or 1.
+ *   Outputs, device.  dst uint8 [T][3][oh][ow] (required); mask bytes [T][oh][ow], valid bytes [T], windows int32 [T][6]
+ *     (each nullable: NULL leaves it out).
+ * The rule (this comment is the specification; integers are 64-bit where a product could pass 2^31):
+ *   1. Tube row of frame t: r = frame_map ? frame_map[t] : t.
+ *   2. The frame is EMPTY when r is outside [0, n_tube), when span is given and r is outside [span[0], span[1]], when a
+ *      coordinate of box r is not finite, or when a later step says so.
+ *   3. Rounding is td_tube_overlay's: finite values clamped to +-2^20, then x0 = (int)floorf(bx0 + 0.5f), y0, x1, y1 alike, in
+ *      fp32.  Empty if x1 <= x0 or y1 <= y0.
+ *   4. Margin: bw = x1 - x0, bh = y1 - y0; mx = (bw margin_num) / margin_den, my = (bh margin_num) / margin_den (integer
+ *      division); x0 -= mx, x1 += mx, y0 -= my, y1 += my.
+ *   5. Clamp to the frame: wx0 = max(x0, 0), wx1 = min(x1, sw), wy0 = max(y0, 0), wy1 = min(y1, sh); cw = wx1 - wx0,
+ *      ch = wy1 - wy0.  Empty if cw <= 0 or ch <= 0.
+ *   6. Output size.  keep_aspect = 0: rh = oh, rw = ow.  keep_aspect = 1: if cw oh >= ch ow then rw = ow and
+ *      rh = min(oh, max(1, (2 ch ow + cw) / (2 cw))), else rh = oh and rw = min(ow, max(1, (2 cw oh + ch) / (2 ch))).
+ *   7. Pixels.  For y < rh and x < rw, dst[t][c][y][x] is, byte for byte, what td_clip_resample writes for the job whose
+ *      source is the ch x cw sub-image at (wy0, wx0) of the frame (I420 / NV12 frames converted to rgb24 by the integer rule
+ *      above first, the chroma sample of source pixel (y, x) being (y >> 1, x >> 1) OF THE FRAME, not of the sub-image), with
+ *      flip = 0, virtual size rh x rw, the window all of it, planar = 1, H = oh, W = ow.  Every other byte of the frame's
+ *      3 oh ow is 0; mask is 0 inside rh x rw and 1 outside: the collate's bottom / right padding, so the crops have the
+ *      uint8 video + mask layout of a staged batch.
+ *   8. A frame that is not empty has valid[t] = 1 and windows[t] = (wy0, wx0, ch, cw, rh, rw): the record that maps a
+ *      second stage's results back into the frame.
+ *   9. An empty frame has pixels all 0, mask all 1, valid[t] = 0 and a window of six zeros.
+ * No byte outside the job's dst / mask / valid / windows extents is written; no byte outside the source rows of the job's T
+ * frames is read.  One launch for any number of jobs; no allocation, no synchronisation, no atomics.
+ * Limits: sh 1..16384; sw 1..8192 (the window can be the whole row: td_clip_resample_src's row bound); oh, ow 1..4096;
+ * T >= 0; n_tube >= 1; margin_den 1..1024, margin_num 0..4 margin_den; and two staged rows of sw pixels plus the column table
+ * of ow entries must fit 64 KiB of LDS (6 sw + 8 ow <= 65380 is enough: any ow at sw <= 5400, any sw at ow <= 2000; td_clip_resample
+ * refuses the same whole-row window for the same reason).  A
+ * violation returns an error whose message names the field; nothing is launched.  `jobs` is a host array consumed before the
+ * call returns; the job table lives in caller-provided memory as for td_tube_overlay (table_host page-locked, table_dev
+ * device memory, both of td_tube_crop_table_bytes(n_jobs) bytes). */
+typedef struct td_crop_job {
+  const void* plane0; /* rgb24 pixels, or Y */
+  const void* plane1; /* I420: U; NV12: UV pairs; RGB24: ignored */
+  const void* plane2; /* I420: V; else ignored */
+  long long frame_stride;
+  int pitch0, pitch1, pitch2;
+  int fmt;
+  int matrix, full_range; /* I420 / NV12 only */
+  int T, sh, sw;
+  const float* boxes;
+  const long long* span;
+  const int* frame_map;
+  int n_tube;
+  int oh, ow;
+  int margin_num, margin_den;
+  int keep_aspect;
+  void* dst;
+  void* mask;
+  unsigned char* valid;
+  int* windows;
+} td_crop_job;
+size_t td_tube_crop_table_bytes(int n_jobs);
+int td_tube_crop(const td_crop_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,13 @@ class OverlayJob(C.Structure):
                [(n, C.c_int) for n in ("n_tube", "mh", "mw", "thickness", "heat_alpha", "dim_alpha")] + [(n, C.c_ubyte * 3) for n in ("box_color", "heat_color", "dim_color")]
 
 
+class CropJob(C.Structure):
+    """td_crop_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("plane0", "plane1", "plane2")] + [("frame_stride", C.c_longlong)] + \
+               [(n, C.c_int) for n in ("pitch0", "pitch1", "pitch2", "fmt", "matrix", "full_range", "T", "sh", "sw")] + [(n, C.c_void_p) for n in ("boxes", "span", "frame_map")] + \
+               [(n, C.c_int) for n in ("n_tube", "oh", "ow", "margin_num", "margin_den", "keep_aspect")] + [(n, C.c_void_p) for n in ("dst", "mask", "valid", "windows")]
+
+
 class ReplicaMapsOut(C.Structure):
     """td_replica_maps_out."""
     _fields_ = [(n, C.c_void_p) for n in ("owner", "vid_of_frame", "vid_of_clip", "query_mask", "frame_dest", "clip_of", "vis_src", "vis_dst", "txt_src", "txt_dst",
@@ -156,6 +163,7 @@ _SIGS = {
     "td_replica_maps": [_P, _I, _I, _I, _I, _I, _I, C.POINTER(ReplicaMapsOut), _P],
     "td_tube_overlay": [C.POINTER(OverlayJob), _I, _P, _P, _SZ, _P],
     "td_sted_topk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "td_tube_crop": [C.POINTER(CropJob), _I, _P, _P, _SZ, _P],
 }
 _SIZE_SIGS = {
     "td_grad_norm_ws_bytes": [],
@@ -164,6 +172,7 @@ _SIZE_SIGS = {
     "td_clip_resample_table_bytes": [_I],
     "td_clip_resample_src_table_bytes": [_I],
     "td_tube_overlay_table_bytes": [_I],
+    "td_tube_crop_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],

@@ -1,4 +1,5 @@
-"""Grounded tubes drawn into decoded frames on the device (td_tube_overlay, csrc/overlay.hip).
+"""Grounded tubes drawn into decoded frames on the device (td_tube_overlay, csrc/overlay.hip) and cropped out of them
+(td_tube_crop, csrc/tube_crop.hip: ``crop_tubes`` at the end of this file).
 
 The reference shows an answer on the host: demo_stvg.py:152-194 and server_stvg.py:218-257 re-decode the video to JPEGs,
 open every frame in matplotlib, draw one rectangle and save the JPEG again.  Here the decoded frames stay on the device in
@@ -10,7 +11,7 @@ stated in include/tubedetr_hip.h; so is the colour conversion of ``color_in_spac
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -314,6 +315,144 @@ def annotate(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=No
     _tables.append((host, dev, ev))
     stream = torch.cuda.current_stream(device)
     for group in keep:  # contiguous() may have made copies: the allocator must not hand them out before the launch has run
+        for t in group:
+            if t is not None:
+                t.record_stream(stream)
+    return results[0] if single else results
+
+
+# ---- grounded tubes cropped out of decoded frames (td_tube_crop, csrc/tube_crop.hip) ----------------------------------------
+MAX_CROP_SRC_COLS = 8192
+MAX_CROP_SIDE = 4096
+MAX_MARGIN_DEN = 1024
+
+
+class TubeCrops(NamedTuple):
+    """What ``crop_tubes`` returns for one clip: the crops in the uint8 video + mask layout of a staged batch."""
+    pixels: torch.Tensor   # uint8 (T, 3, oh, ow): the resized window in the top-left rh x rw, zeros elsewhere
+    mask: torch.Tensor     # bool (T, oh, ow): True on the padding
+    valid: torch.Tensor    # bool (T,): False for a frame without a crop (outside the span, no tube row, a degenerate box)
+    windows: torch.Tensor  # int32 (T, 6): (wy0, wx0, ch, cw, rh, rw) - source window and resized size; zeros when not valid
+
+
+def _crop_geometry(size, margin, keep_aspect):
+    try:
+        oh, ow = size
+        num, den = margin
+    except (TypeError, ValueError):
+        raise ValueError(f"size {size!r} and margin {margin!r}: two integers each") from None
+    if any(isinstance(v, bool) or int(v) != v for v in (oh, ow, num, den)):
+        raise ValueError(f"size {size!r} and margin {margin!r}: two integers each")
+    oh, ow, num, den = int(oh), int(ow), int(num), int(den)
+    if not (1 <= oh <= MAX_CROP_SIDE and 1 <= ow <= MAX_CROP_SIDE):
+        raise ValueError(f"size {oh} x {ow}: sides in 1..{MAX_CROP_SIDE}")
+    if not 1 <= den <= MAX_MARGIN_DEN:
+        raise ValueError(f"margin denominator {den}: 1..{MAX_MARGIN_DEN}")
+    if not 0 <= num <= 4 * den:
+        raise ValueError(f"margin {num}/{den}: between 0 and 4")
+    if keep_aspect not in (0, 1, False, True):
+        raise ValueError(f"keep_aspect {keep_aspect!r}: a bool")
+    return oh, ow, num, den, int(bool(keep_aspect))
+
+
+def crop_job(src: int, T: int, sh: int, sw: int, boxes: int, n_tube: int, dst: int, size: Tuple[int, int] = (224, 224), pix_fmt: str = "rgb24", matrix: str = "bt601",
+             full_range: bool = False, span: Optional[int] = None, frame_map: Optional[int] = None, margin: Tuple[int, int] = (0, 1), keep_aspect: bool = True,
+             mask: Optional[int] = None, valid: Optional[int] = None, windows: Optional[int] = None,
+             planes: Optional[Sequence[int]] = None, pitches: Optional[Sequence[int]] = None, frame_stride: Optional[int] = None):
+    """One ``td_crop_job``: T frames of sh x sw in ``pix_fmt`` at device address ``src``, the tube ``boxes`` (fp32 [n_tube][4];
+    ``span`` int64 [2] and ``frame_map`` int32 [T] or None) cropped into ``dst`` (uint8 [T][3][oh][ow]); ``mask`` ([T][oh][ow]),
+    ``valid`` ([T]) and ``windows`` (int32 [T][6]) are device addresses or None.  Without ``planes`` / ``pitches`` /
+    ``frame_stride`` the frames are tightly packed (``DeviceFrames``); else the planes are the device addresses of frame 0's
+    planes and the pitches their row pitches."""
+    from . import _hip
+
+    T, sh, sw, n_tube = int(T), int(sh), int(sw), int(n_tube)
+    _check_geometry(pix_fmt, T, sh, sw)
+    if sw > MAX_CROP_SRC_COLS:
+        raise ValueError(f"frame width {sw}: at most {MAX_CROP_SRC_COLS} for a crop (the window can be the whole row)")
+    if matrix not in _MATRICES:
+        raise ValueError(f"matrix {matrix!r}: one of {_MATRICES}")
+    if n_tube < 1:
+        raise ValueError(f"n_tube = {n_tube}: at least one tube row")
+    if not boxes or not dst:
+        raise ValueError("boxes and dst are device addresses, not None")
+    oh, ow, num, den, keep = _crop_geometry(size, margin, keep_aspect)
+    fmt, tight, sizes = _planes(pix_fmt, sh, sw)
+    j = _hip.CropJob()
+    (j.plane0, j.plane1, j.plane2), (j.pitch0, j.pitch1, j.pitch2), j.frame_stride = _describe(src, sizes, tight, planes, pitches, frame_stride)
+    j.fmt, j.matrix, j.full_range = fmt, _MATRICES.index(matrix), int(bool(full_range))
+    j.T, j.sh, j.sw = T, sh, sw
+    j.boxes, j.span, j.frame_map, j.n_tube = boxes, span, frame_map, n_tube
+    j.oh, j.ow, j.margin_num, j.margin_den, j.keep_aspect = oh, ow, num, den, keep
+    j.dst, j.mask, j.valid, j.windows = dst, mask, valid, windows
+    return j
+
+
+def tube_crop(jobs: Sequence, device) -> tuple:
+    """One td_tube_crop launch on the current stream with freshly allocated job tables; returns them: the caller keeps them
+    alive until the stream has passed the launch (``crop_tubes`` recycles its own instead)."""
+    from . import _hip
+
+    lib = _hip.lib()
+    nb = int(lib.td_tube_crop_table_bytes(len(jobs)))
+    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
+    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
+    arr = (_hip.CropJob * len(jobs))(*jobs)
+    _hip.check(lib.td_tube_crop(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_tube_crop")
+    return host, dev
+
+
+def crop_tubes(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=None, frame_map=None, size: Tuple[int, int] = (224, 224),
+               margin: Tuple[int, int] = (0, 1), keep_aspect: bool = True):
+    """Crop grounded tubes out of decoded frames: ONE launch for one clip or for a list of clips (then ``boxes``, ``span`` and
+    ``frame_map`` are lists too, or None; the same clip may appear several times, once per tube).  Per clip:
+      boxes      fp32 (n_tube, 4) xyxy in the frames' pixels on the device: what ``PostProcess`` returned for the clip, stacked;
+      span       int64 (2,): the clip's row of ``sted_decode``'s output; frames outside it get no crop; None: all rows;
+      frame_map  int32 (T,): the tube row of each frame; None: frame t is row t.
+    ``size`` = (oh, ow) of every crop; ``margin`` = (num, den): context of num / den of the box side added on every side before
+    the window is clamped to the frame; ``keep_aspect``: the window keeps its shape inside oh x ow (padded at the bottom /
+    right, ``mask`` True there) instead of being stretched.  The rule is exact and stated in include/tubedetr_hip.h.
+    Returns ``TubeCrops`` (a list for a list).  Nothing here synchronises or copies to the host."""
+    from . import _hip
+
+    single = isinstance(frames, DeviceFrames)
+    clips = [frames] if single else list(frames)
+    n = len(clips)
+    if n == 0:
+        return []
+    if not isinstance(clips[0], DeviceFrames):
+        raise ValueError("frames: DeviceFrames on one device")
+    device = clips[0].data.device
+    oh, ow, num, den, keep = _crop_geometry(size, margin, keep_aspect)
+    boxes_l, span_l, map_l = (_as_list(v, n, k) for v, k in ((boxes, "boxes"), (span, "span"), (frame_map, "frame_map")))
+    jobs, keep_alive, results = [], [], []
+    for c, b, s, m in zip(clips, boxes_l, span_l, map_l):
+        if not isinstance(c, DeviceFrames) or c.data.device != device:
+            raise ValueError("frames: DeviceFrames on one device")
+        if b is None:
+            raise ValueError("boxes: a torch.float32 tensor (n_tube, 4) per clip")
+        b = _dev_tensor(b, torch.float32, (4,), "boxes", device)
+        s = _dev_tensor(s, torch.int64, (2,), "span", device)
+        m = _dev_tensor(m, torch.int32, (c.T,), "frame_map", device)
+        if b.dim() != 2 or b.shape[0] < 1 or s is not None and s.dim() != 1 or m is not None and m.dim() != 1:
+            raise ValueError("boxes (n_tube, 4) with n_tube >= 1, span (2,), frame_map (T,)")
+        pixels = torch.empty((c.T, 3, oh, ow), dtype=torch.uint8, device=device)
+        mask = torch.empty((c.T, oh, ow), dtype=torch.bool, device=device)
+        valid = torch.empty((c.T,), dtype=torch.bool, device=device)
+        windows = torch.empty((c.T, 6), dtype=torch.int32, device=device)
+        jobs.append(crop_job(c.data.data_ptr(), c.T, c.h, c.w, b.data_ptr(), b.shape[0], pixels.data_ptr(), (oh, ow), c.pix_fmt, c.matrix, c.full_range,
+                             _hip.ptr(s), _hip.ptr(m), (num, den), bool(keep), mask.data_ptr(), valid.data_ptr(), windows.data_ptr()))
+        keep_alive.append((c.data, b, s, m))
+        results.append(TubeCrops(pixels, mask, valid, windows))
+    lib = _hip.lib()
+    nb = int(lib.td_tube_crop_table_bytes(n))
+    host, dev, ev = _take_table(nb, device)
+    arr = (_hip.CropJob * n)(*jobs)
+    _hip.check(lib.td_tube_crop(arr, n, host.data_ptr(), dev.data_ptr(), host.numel(), _hip.stream_ptr()), "td_tube_crop")
+    ev.record()
+    _tables.append((host, dev, ev))
+    stream = torch.cuda.current_stream(device)
+    for group in keep_alive:  # contiguous() may have made copies: the allocator must not hand them out before the launch has run
         for t in group:
             if t is not None:
                 t.record_stream(stream)
