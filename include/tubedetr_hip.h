@@ -441,7 +441,12 @@ typedef struct td_optim_segment {
 } td_optim_segment;
 /* Replaces torch.nn.utils.clip_grad_norm_ (engine.py:149-150): norm_clip[0] = L2 norm of all active gradients,
  * norm_clip[1] = min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0); *step (device int, may be NULL) += 1.
- * ws: td_grad_norm_ws_bytes() bytes of device scratch.  Two launches. */
+ * ws: td_grad_norm_ws_bytes() bytes of device scratch.  Two launches.
+ * A non-finite active gradient is NOT detected here, and the step counter advances all the same.  A NaN element makes
+ * the norm and the coefficient NaN (max_norm > 0), and the td_adamw_ema_step that follows multiplies every gradient by it:
+ * every active param, both moments and the EMA are NaN after one launch.  An Inf element (or finite gradients whose fp32
+ * norm overflows) makes the norm Inf and the coefficient 0: Inf * 0 = NaN lands in that element's param / moments / EMA,
+ * every other element takes a zero-gradient step.  td_grad_norm_clip_guarded (below) is the call that notices. */
 size_t td_grad_norm_ws_bytes(void);
 int td_grad_norm_clip(const float* grad, size_t n, const td_optim_segment* segs, int n_segs, float max_norm, void* ws,
                       size_t ws_bytes, float* norm_clip, int* step, td_stream_t stream);
@@ -455,6 +460,50 @@ int td_adamw_ema_step(float* param, const float* grad, float* exp_avg, float* ex
                       const td_optim_segment* segs, int n_segs, const float* lr_dev, const float* norm_clip,
                       const int* step_dev, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
                       td_stream_t stream);
+/* The same tail with a guard: a step whose gradient norm is not finite is skipped ON THE DEVICE, without a host
+ * synchronisation, so the pair can be captured in a HIP graph (replaces the host-side `if not math.isfinite(loss_value):
+ * sys.exit(1)` of engine.py:142-145, which a replayed graph never reaches).  Opt-in: the two calls above are unchanged.
+ * guard: td_guard_bytes(history) bytes of device memory, 4-byte aligned, zero-filled ONCE by the caller and then owned by
+ * these calls: a 16-byte header `int attempts, skipped, consecutive_skipped, applied_now`, followed by a ring of `history`
+ * td_step_record (0 <= history <= TD_GUARD_HISTORY_MAX; 0: counters only).
+ * td_grad_norm_clip_guarded: the total is accumulated exactly as td_grad_norm_clip accumulates it (same grid, same order,
+ * same reductions), so on a finite buffer norm_clip[0..1] and *step are bit-identical to that call's; the per-group sums
+ * are extra accumulators of the same pass.  ws: td_grad_norm_guard_ws_bytes() bytes, 8-byte aligned (per-workgroup
+ * partial sums of the total and of each of the TD_OPTIM_MAX_GROUPS groups).  The decision is isfinite() of the fp32 norm
+ * that is written to norm_clip[0]:
+ *   finite:     norm_clip[1] as above, *step += 1, applied_now = 1, consecutive_skipped = 0;
+ *   not finite: norm_clip[0] = the norm as computed (NaN / Inf), norm_clip[1] = 0, *step untouched, applied_now = 0,
+ *               skipped += 1, consecutive_skipped += 1.
+ * Either way attempts += 1 and, if history > 0, ring[(attempts - 1) % history] = {attempts, *step after the call (0 if
+ * step is NULL), applied_now, norm, coefficient, loss[0] (NaN if loss is NULL), group_norm[g] = sqrt(sum of squares
+ * over group g's active elements), 0 for a group without any}.  Stale NaN / Inf in inactive segments does not count,
+ * as above.
+ * `loss` (device float, may be NULL) is RECORDED and never decides: under data parallelism the loss is a per-rank value,
+ * while the gradient buffer is the exchanged one and identical on every rank.  A decision taken from the loss could differ
+ * between ranks - one applies the update, another skips it - and the replicas' weights would part for good; the norm of
+ * the exchanged buffer gives every rank the same decision from the same bits.
+ * td_adamw_ema_step_guarded: td_adamw_ema_step's kernel body behind one read of applied_now per workgroup.  applied_now
+ * == 0: it returns before any load or store of param / exp_avg / exp_avg_sq / ema, all four stay bit-identical, the EMA
+ * of inactive segments included (the batch counts as never seen); applied_now == 1: bit-identical to td_adamw_ema_step. */
+#define TD_GUARD_HISTORY_MAX 4096
+typedef struct td_step_record {
+  int attempt;  /* 1-based number of the td_grad_norm_clip_guarded call that wrote the record */
+  int step;     /* the step counter after that call: it counts applied updates only */
+  int applied;  /* 1: the update ran; 0: skipped */
+  float norm;   /* norm_clip[0] */
+  float clip;   /* norm_clip[1] */
+  float loss;   /* loss[0] as handed over, NaN if none */
+  float group_norm[TD_OPTIM_MAX_GROUPS];
+} td_step_record;
+size_t td_grad_norm_guard_ws_bytes(void);
+size_t td_guard_bytes(int history);
+int td_grad_norm_clip_guarded(const float* grad, size_t n, const td_optim_segment* segs, int n_segs, float max_norm, void* ws,
+                              size_t ws_bytes, float* norm_clip, int* step, const float* loss, void* guard, int history,
+                              td_stream_t stream);
+int td_adamw_ema_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, size_t n,
+                              const td_optim_segment* segs, int n_segs, const float* lr_dev, const float* norm_clip,
+                              const int* step_dev, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                              const void* guard, td_stream_t stream);
 
 /* ---- SetCriterion as one launch ------------------------------------------------------------------
  * The 24 losses of models/tubedetr.py:270-372,397-460 (L1 + GIoU over the annotated frames' boxes, start / end KL

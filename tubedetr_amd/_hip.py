@@ -50,6 +50,16 @@ class OptimSegment(C.Structure):
     _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("group", C.c_int), ("active", C.c_int)]
 
 
+TD_OPTIM_MAX_GROUPS = 4
+TD_GUARD_HISTORY_MAX = 4096
+
+
+class StepRecord(C.Structure):
+    """td_step_record."""
+    _fields_ = [("attempt", C.c_int), ("step", C.c_int), ("applied", C.c_int), ("norm", C.c_float), ("clip", C.c_float), ("loss", C.c_float),
+                ("group_norm", C.c_float * TD_OPTIM_MAX_GROUPS)]
+
+
 class ResampleJob(C.Structure):
     """td_resample_job."""
     _fields_ = [("src", C.c_void_p), ("src_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("src_pitch", "T", "sh", "sw", "flip", "rh", "rw", "wy", "wx", "wh", "ww")] + \
@@ -148,6 +158,8 @@ _SIGS = {
     "td_sted_decode": [_P, _P, _I, _I, _P],
     "td_grad_norm_clip": [_P, _SZ, C.POINTER(OptimSegment), _I, _F, _P, _SZ, _P, _P, _P],
     "td_adamw_ema_step": [_P, _P, _P, _P, _P, _SZ, C.POINTER(OptimSegment), _I, _P, _P, _P, _F, _F, _F, _F, _F, _P],
+    "td_grad_norm_clip_guarded": [_P, _SZ, C.POINTER(OptimSegment), _I, _F, _P, _SZ, _P, _P, _P, _P, _I, _P],
+    "td_adamw_ema_step_guarded": [_P, _P, _P, _P, _P, _SZ, C.POINTER(OptimSegment), _I, _P, _P, _P, _F, _F, _F, _F, _F, _P, _P],
     "td_mha_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _U32, _P, _I, _P],
     "td_mha_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _U32, _P, _I, _P],
     "td_cross_q1_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _U32, _P, _I, _P],
@@ -167,6 +179,8 @@ _SIGS = {
 }
 _SIZE_SIGS = {
     "td_grad_norm_ws_bytes": [],
+    "td_grad_norm_guard_ws_bytes": [],
+    "td_guard_bytes": [_I],
     "td_mha_lean_stats_bytes": [_I, _I, _I],
     "td_conv_wgrad_batch_table_bytes": [_I],
     "td_clip_resample_table_bytes": [_I],

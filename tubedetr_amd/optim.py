@@ -13,6 +13,10 @@ the state_dict stay what they were); gradients are taken from the flat buffer of
 (``FlatGradAllReducer``, gathered there anyway) or gathered with one fused multi-tensor copy; Adam moments and the EMA
 copy are flat buffers of the same shape.  An ``ema_model`` (the reference keeps ``deepcopy(model)``) is re-pointed at the
 EMA buffer the same way, so evaluation / checkpointing code reading it needs no change.
+
+``skip_nonfinite=True`` replaces the reference's host-side abort on a non-finite loss (engine.py:142-145) with a decision
+taken on the device from the gradient norm: such a step changes nothing and is counted and recorded in a guard block that
+``poll()`` / ``raise_if_stuck()`` / ``guard_snapshot()`` read.
 """
 from __future__ import annotations
 
@@ -69,10 +73,32 @@ def adjust_learning_rate(optimizer, epoch: int, curr_step: int, num_training_ste
         group["lr"] = lr * gm
 
 
+class NonFiniteStepError(RuntimeError):
+    """``FusedAdamWEMA.raise_if_stuck``: that many optimizer steps in a row were skipped because the gradient norm was not
+    finite (the reference's ``sys.exit(1)`` on a non-finite loss, engine.py:142-145, as an exception a driver can catch)."""
+
+
+_GUARD_HEADER_INTS = 4  # int attempts, skipped, consecutive_skipped, applied_now (include/tubedetr_hip.h)
+
+
+def _record_dict(r: "_hip.StepRecord") -> dict:
+    return {"attempt": r.attempt, "step": r.step, "applied": bool(r.applied), "norm": r.norm, "clip": r.clip, "loss": r.loss,
+            "group_norm": list(r.group_norm)}
+
+
+def _decode_guard(raw: bytes, history: int) -> dict:
+    """The guard block as td_grad_norm_clip_guarded keeps it -> counters, the newest record, the ring oldest first."""
+    attempts, skipped, consecutive, _ = (C.c_int * _GUARD_HEADER_INTS).from_buffer_copy(raw[:16])
+    ring = (_hip.StepRecord * history).from_buffer_copy(raw[16 : 16 + history * C.sizeof(_hip.StepRecord)]) if history else ()
+    records = [_record_dict(ring[(a - 1) % history]) for a in range(max(1, attempts - history + 1), attempts + 1)] if history else []
+    return {"attempts": attempts, "skipped": skipped, "consecutive_skipped": consecutive, "last": records[-1] if records else None, "history": records}
+
+
 class FusedAdamWEMA:
     def __init__(self, model: torch.nn.Module, lr: float = 5e-5, lr_backbone: float = 1e-5, text_encoder_lr: float = 5e-5,
                  weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, max_norm: float = 0.1,
-                 ema_model: Optional[torch.nn.Module] = None, ema_decay: float = 0.9998, reducer=None):
+                 ema_model: Optional[torch.nn.Module] = None, ema_decay: float = 0.9998, reducer=None,
+                 skip_nonfinite: bool = False, history: int = 64):
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         self.names = [n for n, _ in named]
         self.params: List[torch.nn.Parameter] = [p for _, p in named]
@@ -125,7 +151,20 @@ class FusedAdamWEMA:
         self._lr_last = None
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.norm_clip = torch.zeros(2, dtype=torch.float32, device=dev)  # [total gradient norm, clip coefficient] of the last step
-        self._ws = torch.empty(_hip.lib().td_grad_norm_ws_bytes(), dtype=torch.uint8, device=dev)
+        # skip_nonfinite: the guarded pair of launches (td_grad_norm_clip_guarded / td_adamw_ema_step_guarded) decides on the
+        # device whether the step is applied; counters and the last `history` steps' records live in the guard block
+        self.skip_nonfinite, self.history = bool(skip_nonfinite), int(history)
+        self._guard = None
+        L = _hip.lib()
+        if self.skip_nonfinite:
+            if not 0 <= self.history <= _hip.TD_GUARD_HISTORY_MAX:
+                raise ValueError(f"history must be in 0..{_hip.TD_GUARD_HISTORY_MAX}, got {history}")
+            self._ws = torch.empty(L.td_grad_norm_guard_ws_bytes(), dtype=torch.uint8, device=dev)
+            self._guard = torch.zeros(L.td_guard_bytes(self.history), dtype=torch.uint8, device=dev)
+            self._polls = []        # poll(): [pinned copy of the guard block, event behind the copy], oldest first
+            self._poll_newest = None  # the newest copy whose event has completed
+        else:
+            self._ws = torch.empty(L.td_grad_norm_ws_bytes(), dtype=torch.uint8, device=dev)
         self._active = None
         self._loaded_active = None  # load_state_dict: which parameters the checkpoint held state for (until the first step decides)
         self._segs = None
@@ -150,11 +189,21 @@ class FusedAdamWEMA:
             p.grad = None
 
     @torch.no_grad()
-    def step(self):
+    def step(self, loss: Optional[torch.Tensor] = None):
         """clip_grad_norm_ + AdamW.step + update_ema.  Parameters whose ``.grad`` is None keep their value and moments, like
         torch leaves them, and stay out of the norm; their EMA still moves towards them, as update_ema moves every entry
         (it matters once ``ema_model`` was loaded separately).  A change of which parameters those are rebuilds the segments;
-        there is one step counter, so a parameter that starts late gets the global t in its bias corrections (torch: its own)."""
+        there is one step counter, so a parameter that starts late gets the global t in its bias corrections (torch: its own).
+
+        ``skip_nonfinite=True``: a step whose gradient norm is not finite changes nothing - parameters, moments, EMA and the
+        step counter stay bit for bit - and is counted in the guard block; the decision is taken on the device from the flat
+        gradient buffer (the same bits on every rank), nothing here waits for it.  ``loss`` (a device fp32 scalar, guarded
+        mode only) goes into the step's record and decides nothing: it is a per-rank value."""
+        if loss is not None:
+            if not self.skip_nonfinite:
+                raise ValueError("step(loss=...) records the loss in the guard block: build the optimizer with skip_nonfinite=True")
+            if not (loss.is_cuda and loss.dtype == torch.float32 and loss.numel() == 1):
+                raise ValueError("loss must be a device fp32 scalar")
         grads = [p.grad for p in self.params]
         active = [g is not None for g in grads]
         if active != self._active:
@@ -176,13 +225,55 @@ class FusedAdamWEMA:
             self._lr_last = lrs
         L = _hip.lib()
         st = _hip.stream_ptr()
-        _hip.check(L.td_grad_norm_clip(self.flat_g.data_ptr(), self.numel, self._segs, len(self._segs), self.max_norm, self._ws.data_ptr(),
-                                       self._ws.numel(), self.norm_clip.data_ptr(), self.step_dev.data_ptr(), st), "td_grad_norm_clip")
-        _hip.check(L.td_adamw_ema_step(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                       self.ema.data_ptr() if self.ema is not None else None, self.numel, self._segs, len(self._segs),
-                                       self._lr_dev.data_ptr(), self.norm_clip.data_ptr(), self.step_dev.data_ptr(), self.betas[0], self.betas[1],
-                                       self.eps, self.weight_decay, self.ema_decay, st), "td_adamw_ema_step")
+        norm_args = (self.flat_g.data_ptr(), self.numel, self._segs, len(self._segs), self.max_norm, self._ws.data_ptr(), self._ws.numel(),
+                     self.norm_clip.data_ptr(), self.step_dev.data_ptr())
+        adam_args = (self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                     self.ema.data_ptr() if self.ema is not None else None, self.numel, self._segs, len(self._segs), self._lr_dev.data_ptr(),
+                     self.norm_clip.data_ptr(), self.step_dev.data_ptr(), self.betas[0], self.betas[1], self.eps, self.weight_decay, self.ema_decay)
+        if self.skip_nonfinite:
+            _hip.check(L.td_grad_norm_clip_guarded(*norm_args, loss.data_ptr() if loss is not None else None, self._guard.data_ptr(), self.history, st),
+                       "td_grad_norm_clip_guarded")
+            _hip.check(L.td_adamw_ema_step_guarded(*adam_args, self._guard.data_ptr(), st), "td_adamw_ema_step_guarded")
+        else:
+            _hip.check(L.td_grad_norm_clip(*norm_args, st), "td_grad_norm_clip")
+            _hip.check(L.td_adamw_ema_step(*adam_args, st), "td_adamw_ema_step")
         invalidate_prepared()  # the kernels changed the weights behind torch's version counters: prepared bf16 copies are stale
+
+    # ---- the guard block: counters and the ring of step records (skip_nonfinite=True) ----
+    def _need_guard(self):
+        if self._guard is None:
+            raise RuntimeError("no guard block: build the optimizer with skip_nonfinite=True")
+
+    def guard_snapshot(self) -> dict:
+        """One BLOCKING device-to-host copy of the guard block -> {"attempts", "skipped", "consecutive_skipped", "last": the
+        newest record or None, "history": at most ``history`` records, oldest first}; a record is {"attempt", "step" (applied
+        updates so far), "applied", "norm", "clip", "loss" (NaN if none was handed over), "group_norm": one per group}."""
+        self._need_guard()
+        return _decode_guard(self._guard.cpu().numpy().tobytes(), self.history)
+
+    def poll(self) -> Optional[dict]:
+        """Never blocks: enqueues an async copy of the guard block into a pinned buffer behind an event and returns the newest
+        snapshot whose event has completed (``guard_snapshot``'s format), None before the first one.  What it returns is
+        therefore a few steps old while the host runs ahead of the stream."""
+        self._need_guard()
+        while self._polls and self._polls[0][1].query():
+            self._poll_newest = self._polls.pop(0)[0]
+        if len(self._polls) < 8:  # (a host far ahead of the stream keeps at most 8 copies in flight)
+            host = torch.empty(self._guard.numel(), dtype=torch.uint8).pin_memory()
+            host.copy_(self._guard, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._polls.append((host, ev))
+        return None if self._poll_newest is None else _decode_guard(self._poll_newest.numpy().tobytes(), self.history)
+
+    def raise_if_stuck(self, max_consecutive: int) -> None:
+        """Raises NonFiniteStepError when the snapshot ``poll()`` returns shows at least ``max_consecutive`` skipped steps in
+        a row; the message carries the last records.  Call it every N iterations in place of engine.py:142-145."""
+        snap = self.poll()
+        if snap is not None and snap["consecutive_skipped"] >= max_consecutive:
+            last = "\n".join(f"  {r}" for r in snap["history"][-8:]) or "  (history = 0: no records kept)"
+            raise NonFiniteStepError(f"{snap['consecutive_skipped']} optimizer steps in a row skipped for a non-finite gradient norm "
+                                     f"({snap['skipped']} of {snap['attempts']} attempts skipped in all); last records:\n{last}")
 
     # ---- checkpointing: torch.optim.AdamW's own layout (what the reference stores in checkpoint["optimizer"], main.py:681) ----
     def _torch_order(self) -> List[int]:
@@ -192,7 +283,9 @@ class FusedAdamWEMA:
     def state_dict(self):
         """{"state": {index: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...]} exactly like
         ``torch.optim.AdamW(param_dicts).state_dict()``: a checkpoint written here resumes in the reference and vice versa.
-        (The EMA weights are not optimizer state: they live in ``ema_model.state_dict()``, checkpoint["model_ema"].)"""
+        (The EMA weights are not optimizer state: they live in ``ema_model.state_dict()``, checkpoint["model_ema"].)
+        With ``skip_nonfinite`` the layout is the same: "step" counts APPLIED updates only (a skipped step does not move the
+        device counter), and the guard block's counters and records are not stored."""
         order = self._torch_order()
         step = float(self.step_dev.item())
         # which parameters have state: those the step has updated; before the first step after a resume, those the loaded
@@ -217,6 +310,9 @@ class FusedAdamWEMA:
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
+        if self._guard is not None:  # the guard's counters and records are diagnostics, not state: a resumed run starts them at zero
+            self._guard.zero_()
+            self._polls, self._poll_newest = [], None
         if "names" in sd and "exp_avg" in sd:  # flat format written by earlier versions of this class
             assert sd["names"] == self.names
             self.exp_avg.copy_(sd["exp_avg"])
