@@ -833,6 +833,34 @@ typedef struct td_crop_job {
 size_t td_tube_crop_table_bytes(int n_jobs);
 int td_tube_crop(const td_crop_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
 
+/* ---- Which kernel a td_conv_gemm / td_linear_ex call would run on (an addition WITHIN ABI 11: nothing above changed) ----
+ * The launching calls plan every launch with one host function and then launch the plan; these two run the same planner and
+ * return the plan instead.  They touch no device (no HIP call; the epilogue's pointers are only tested for NULL), use the
+ * process's dispatch knobs exactly as a launch in the same process would, and take the CU count as an argument (the launching
+ * calls pass the current device's).  `routes` has room for 4 records; *n_routes becomes 1, or 4 for a stride-2 3x3 input
+ * gradient split by output parity.  An argument the launching call refuses is refused here with the same code and message. */
+#define TD_GEMM_KERNEL_TILED 0      /* conv_gemm_kernel */
+#define TD_GEMM_KERNEL_PERSISTENT 1 /* pw_resident2_kernel */
+#define TD_GEMM_KERNEL_BIG8 2       /* conv_gemm_big8_kernel: 256 x 256 tiles */
+#define TD_GEMM_KERNEL_BIG8N 3      /* conv_gemm_big8n_kernel: 256 x 128 tiles */
+#define TD_GEMM_WALK_POINTWISE 0
+#define TD_GEMM_WALK_TAP_UNIFORM 1
+#define TD_GEMM_WALK_GATHER 2
+#define TD_GEMM_WALK_GX 3 /* td_linear_ex's two-source rows */
+typedef struct td_gemm_route {
+  int family;                  /* TD_PROF_* */
+  int kernel;                  /* TD_GEMM_KERNEL_* */
+  int bm, bn;                  /* tile: output rows x output channels */
+  int stages;                  /* tiled kernel: 2 or 3; the others: 0 */
+  int walk;                    /* TD_GEMM_WALK_* */
+  unsigned grid, block;        /* workgroups, threads per workgroup */
+  int dtype;                   /* with the six below: the launch's td_prof_dump record */
+  int M, N, K, R, stride, mode;
+} td_gemm_route;
+int td_conv_gemm_route(const td_conv_desc* d, const td_epilogue* e, int dtype, int n_cu, td_gemm_route* routes, int* n_routes);
+/* has_a2: whether the launching call would pass a second source */
+int td_linear_ex_route(const td_linear_ex_desc* x, int has_a2, const td_epilogue* e, int dtype, int n_cu, td_gemm_route* routes, int* n_routes);
+
 #ifdef __cplusplus
 }
 #endif

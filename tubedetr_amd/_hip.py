@@ -45,6 +45,16 @@ class LinearExDesc(C.Structure):
                [("rows1", C.c_longlong), ("rows2", C.c_longlong)] + [(n, C.c_void_p) for n in ("a1_map", "a2_map", "out_map", "res_map")]
 
 
+class GemmRoute(C.Structure):
+    """td_gemm_route."""
+    _fields_ = [(n, C.c_int) for n in ("family", "kernel", "bm", "bn", "stages", "walk")] + [("grid", C.c_uint), ("block", C.c_uint)] + \
+               [(n, C.c_int) for n in ("dtype", "M", "N", "K", "R", "stride", "mode")]
+
+
+TD_GEMM_KERNEL_TILED, TD_GEMM_KERNEL_PERSISTENT, TD_GEMM_KERNEL_BIG8, TD_GEMM_KERNEL_BIG8N = 0, 1, 2, 3
+TD_GEMM_WALK_POINTWISE, TD_GEMM_WALK_TAP_UNIFORM, TD_GEMM_WALK_GATHER, TD_GEMM_WALK_GX = 0, 1, 2, 3
+
+
 class OptimSegment(C.Structure):
     """td_optim_segment."""
     _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("group", C.c_int), ("active", C.c_int)]
@@ -176,6 +186,8 @@ _SIGS = {
     "td_tube_overlay": [C.POINTER(OverlayJob), _I, _P, _P, _SZ, _P],
     "td_sted_topk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "td_tube_crop": [C.POINTER(CropJob), _I, _P, _P, _SZ, _P],
+    "td_conv_gemm_route": [C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
+    "td_linear_ex_route": [C.POINTER(LinearExDesc), _I, C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
 }
 _SIZE_SIGS = {
     "td_grad_norm_ws_bytes": [],

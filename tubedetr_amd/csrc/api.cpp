@@ -27,6 +27,15 @@ int check_launch(const char* what) {
   return TD_OK;
 }
 
+int cu_count() {
+  static const int n_cu = [] {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus;
+  }();
+  return n_cu;
+}
+
 // ---- launch timing for bench.py's roofline leg ----
 // Off by default (one relaxed atomic load per launch).  When on, records are appended under a mutex and the record a
 // launching thread is filling is remembered per thread, so autograd worker threads may launch concurrently.

@@ -1233,8 +1233,7 @@ static int fill(MhaParams& p, int B, int H, int Lq, int Lk, int hd, int ldq, int
   p.drop_thresh = 0; p.drop_scale = 1.f; p.seed = seed; p.seed_dev = nullptr;
   if (dropout_p > 0.f) {
     TD_REQUIRE(dropout_p < 1.f, "%s: dropout_p must be < 1", who);
-    p.drop_thresh = (uint32_t)((double)dropout_p * 4294967296.0);
-    if (!p.drop_thresh) p.drop_thresh = 1;
+    p.drop_thresh = dropout_threshold(dropout_p);
     p.drop_scale = 1.f / (1.f - dropout_p);
     p.seed_dev = counter;
   }

@@ -788,11 +788,7 @@ extern "C" int td_bottleneck_fused(const void* x, void* out, const void* w1, con
   const long long nt = (long long)N * p.tiles_y * p.tiles_x;
   TD_REQUIRE(nt < 2000000000LL, "td_bottleneck_fused: too many tiles");
   p.n_tiles = (int)nt;
-  static const int n_cu = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-  }();
+  const int n_cu = cu_count();
   hipStream_t st = (hipStream_t)stream;
   const bool prof = prof_on();
   const double rows = (double)N * H * W;

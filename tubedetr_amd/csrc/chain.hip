@@ -499,11 +499,7 @@ extern "C" int td_pw_chain2(const void* y2, const void* w3, const float* b3, con
   TD_REQUIRE(y2 && w3 && b3 && residual && out && w1 && b1 && h1 && M >= 1, "td_pw_chain2: bad arguments");
   TD_REQUIRE(dtype == TD_BF16 && planes == 256, "td_pw_chain2: bf16, planes = 256 (a layer3 bottleneck pair) only");
   TD_REQUIRE((double)M * planes * 4 * 2 < 4294967000.0, "td_pw_chain2: tensor exceeds the 4 GiB buffer-descriptor range");
-  static const int n_cu = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-  }();
+  const int n_cu = cu_count();
   ChainParams p;
   p.y2 = (const char*)y2;
   p.w3 = (const char*)w3;

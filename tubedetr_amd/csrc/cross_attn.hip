@@ -1457,8 +1457,7 @@ static int fill_q1(CrossQ1Params& p, int F, int S, int H, int E, int ldz, float 
   p.F = F; p.S = S; p.ldz = ldz;
   p.drop_scale = 1.f;
   if (dropout_p > 0.f) {
-    p.drop_thresh = (uint32_t)((double)dropout_p * 4294967296.0);
-    if (p.drop_thresh == 0) p.drop_thresh = 1;
+    p.drop_thresh = dropout_threshold(dropout_p);
     p.drop_scale = 1.f / (1.f - dropout_p);
     p.seed = seed;
     p.seed_dev = ctr;

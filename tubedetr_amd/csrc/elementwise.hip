@@ -658,8 +658,7 @@ extern "C" int td_dropout(const void* x, void* y, size_t n, float p, uint32_t se
   hipStream_t st = (hipStream_t)stream;
   unsigned gr = nblk(n);
   if (gr > 4096) gr = 4096;
-  uint32_t thresh = p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u;
-  if (p > 0.f && !thresh) thresh = 1;
+  const uint32_t thresh = dropout_threshold(p);
   float scale = 1.f / (1.f - p);
   TD_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0, "td_dropout: pointers must be 16-byte aligned");
   TD_DISPATCH(dtype, (ew_kernel<u16, 2><<<gr, 256, 0, st>>>((const u16*)x, nullptr, (u16*)y, n, scale, thresh, seed, thresh ? dropout_counter : nullptr)),

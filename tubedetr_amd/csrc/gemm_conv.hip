@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "td_common.h"
+#include "gemm_route.h"
 #include <algorithm>
 #include <vector>
 
@@ -2053,361 +2054,217 @@ __global__ __launch_bounds__(1024, 1) void conv_wgrad_wide_batch_kernel(const Wg
   }
 }
 
-static int validate(const td_conv_desc* d, int dtype, const char* who) {
-  const int vec = dtype == TD_BF16 ? 8 : 4;
-  TD_REQUIRE(dtype == TD_F32 || dtype == TD_BF16, "%s: bad dtype %d", who, dtype);
-  TD_REQUIRE(d->C % vec == 0, "%s: source channels C=%d must be a multiple of %d (pad them)", who, d->C, vec);
-  TD_REQUIRE(d->N > 0 && d->Hs > 0 && d->Ws > 0 && d->Ho > 0 && d->Wo > 0 && d->R > 0 && d->S > 0 && d->stride > 0,
-             "%s: bad geometry", who);
-  TD_REQUIRE((double)d->N * d->Hs * d->Ws * d->C < 2147483647.0, "%s: source tensor exceeds 2^31 elements", who);
-  TD_REQUIRE(!d->aniso || (d->mode == 0 && d->stride_w >= 1 && d->pad_w >= 0 && d->out_sp <= 1), "%s: anisotropic stride / padding is a forward-only geometry", who);
-  return TD_OK;
-}
-
 }  // namespace td
 
 using namespace td;
 
+// ---- host side of td_conv_gemm / td_linear_ex ----
+// Which kernel a call runs on is planned by gemm_route.h: a pure function of the call (descriptor, epilogue flags, dtype, CU count, knobs)
+// that returns a GemmRoute, asserted case by case on the CPU through td_conv_gemm_route / td_linear_ex_route (tests/test_gemm_routes_cpu.py).
+// This file fills GemmParams and launches the route: launch_route is the one place that names the instances of the four GEMM kernels.
+
 static thread_local unsigned long long* g_dbg = nullptr;  // debug hook (tools/stamp_*.py): per calling thread
-static int persist_min_tiles() {
-  static const int v = [] { const char* e = getenv("TD_PW_PERSIST_MIN"); return e ? atoi(e) : 4; }();
-  return v;
-}
 extern "C" int td_debug_set_stamp_buffer(unsigned long long* buf) { g_dbg = buf; return TD_OK; }
 
-// a launch that uses a subset of the column blocks (filter taps) of a larger weight matrix
-struct WeightSubset {
-  int w_ld;          // row stride of the matrix in elements
-  int ntap;          // taps of this launch, in its own (r', s') order
-  int wtap[4];       // their tap indices in the matrix
-  size_t w_bytes;    // addressable bytes from the pointer handed in
-};
-static int conv_gemm_launch(const void* src, const void* wmat, void* out, const td_conv_desc* d, const td_epilogue* e, int dtype,
-                            td_stream_t stream, const WeightSubset* sub);
+// the dispatch knobs, read from the environment once per process
+static const GemmKnobs& gemm_knobs() {
+  static const GemmKnobs knobs = [] {
+    GemmKnobs k;
+    const struct { const char* name; int* value; } vars[] = {
+        {"TD_PW_PERSIST", &k.pw_persist}, {"TD_PW_PERSIST_MIN", &k.pw_persist_min}, {"TD_PW_PERSIST_DROPOUT", &k.pw_persist_dropout},
+        {"TD_CONV_TAP_UNIFORM", &k.conv_tap_uniform}, {"TD_CONV_BIG", &k.conv_big}, {"TD_CONV_BIG_MIN_WG", &k.conv_big_min_wg},
+        {"TD_CONV_TAP_INNER", &k.conv_tap_inner}, {"TD_CONV_BIG_PERSIST", &k.conv_big_persist}, {"TD_CONV_DEEP", &k.conv_deep},
+        {"TD_DGRAD_S2_PARITY", &k.dgrad_s2_parity}, {"TD_WGRAD_BLOCKS", &k.wgrad_blocks}, {"TD_WGRAD_WIDE", &k.wgrad_wide},
+        {"TD_WGRAD_WIDE_MIN_M", &k.wgrad_wide_min_m}, {"TD_WGRAD_SPLIT_STAGES", &k.wgrad_split_stages}};
+    for (const auto& v : vars)
+      if (const char* e = getenv(v.name)) *v.value = atoi(e);
+    return k;
+  }();
+  return knobs;
+}
 
-// Input gradient of a 3x3 / stride 2 / pad 1 convolution (the second conv of a stage's first block), by output parity.  dx pixel
-// (2a + ph, 2b + pw) only receives taps r with ph + 1 - r even: 1 tap per axis for an even coordinate, 2 for an odd one - 9 taps
-// over 4 pixels.  Walked as ONE gather over all 9 taps per output pixel (the generic input-gradient path) three quarters of the
-// MFMAs multiply zero rows: 4.0 ms per 16-clip step for the three such layers.  Here each parity class is a dense stride-1
-// FORWARD-geometry convolution over g with a 1x1 / 1x2 / 2x1 / 2x2 filter whose taps are column blocks of the same w_dgrad matrix
-// (no re-packed weights: the tap-uniform K walk takes a tap -> column-block map), written with output stride 2 at offset (ph, pw).
-static int conv_dgrad_s2_by_parity(const void* g, const void* w_dgrad, void* dx, const td_conv_desc* d, const td_epilogue* e, int dtype,
-                                   td_stream_t stream) {
-  const int Hg = d->Hs, Wg = d->Ws, Co = d->C, H = d->Ho, W = d->Wo;
-  const size_t es = 2, wbytes = (size_t)d->Nc * 9 * Co * es;
-  for (int ph = 0; ph < 2; ++ph)
-    for (int pw = 0; pw < 2; ++pw) {
-      // axis taps in the sub-filter's own order r' = 0, 1 (source offset + r'): even coordinate: r = 1; odd: r' = 0 <-> r = 2, r' = 1 <-> r = 0
-      const int nr = ph ? 2 : 1, ns = pw ? 2 : 1;
-      const int rmap[2] = {ph ? 2 : 1, 0}, smap[2] = {pw ? 2 : 1, 0};
-      td_conv_desc c = {d->N, Hg, Wg, Co, Hg, Wg, nr, ns, 1, 0, 0, d->Nc, d->ldc, 2, H, W};
-      WeightSubset sub;
-      memset(&sub, 0, sizeof(sub));
-      sub.w_ld = 9 * Co;
-      sub.ntap = nr * ns;
-      for (int r = 0; r < nr; ++r)
-        for (int s_ = 0; s_ < ns; ++s_) sub.wtap[r * ns + s_] = rmap[r] * 3 + smap[s_];
-      const size_t ooff = ((size_t)ph * W + pw) * d->ldc * es;
-      td_epilogue ec;
-      memset(&ec, 0, sizeof(ec));
-      if (e) ec = *e;
-      if (ec.residual) ec.residual = (const char*)ec.residual + ooff;
-      if (ec.mask_src) ec.mask_src = (const char*)ec.mask_src + ooff;
-      const char* wp = (const char*)w_dgrad;
-      if (sub.ntap == 1) {  // one tap: its column block by pointer offset (a 1x1 launch has no tap walk)
-        wp += (size_t)sub.wtap[0] * Co * es;
-        sub.wtap[0] = 0;
-      }
-      sub.w_bytes = wbytes - (size_t)(wp - (const char*)w_dgrad);
-      const int rc = conv_gemm_launch(g, wp, (char*)dx + ooff, &c, &ec, dtype, stream, &sub);
-      if (rc) return rc;
-    }
+static int fill_epilogue(GemmParams& p, const td_epilogue* e, const char* who) {
+  p.alpha = 1.f;
+  if (!e) return TD_OK;
+  p.bias = e->bias;
+  p.residual = (const char*)e->residual;
+  p.mask_src = (const char*)e->mask_src;
+  p.relu = e->relu;
+  p.sigmoid = e->sigmoid;
+  if (e->alpha != 0.f) p.alpha = e->alpha;
+  if (e->dropout_p > 0.f) {
+    TD_REQUIRE(e->dropout_p < 1.f, "%s: dropout_p must be < 1", who);
+    p.drop_thresh = dropout_threshold(e->dropout_p);
+    p.drop_scale = 1.f / (1.f - e->dropout_p);
+    p.seed = e->dropout_seed;
+    p.seed_dev = e->dropout_counter;
+  }
   return TD_OK;
 }
 
-extern "C" int td_conv_gemm(const void* src, const void* wmat, void* out, const td_conv_desc* d, const td_epilogue* e,
-                            int dtype, td_stream_t stream) {
-  TD_REQUIRE(src && wmat && out && d, "td_conv_gemm: null pointer");
-  static const int parity = [] { const char* e_ = getenv("TD_DGRAD_S2_PARITY"); return e_ ? atoi(e_) : 1; }();  // (A/B: 0 = one gather over all 9 taps)
-  if (parity && dtype == TD_BF16 && d->mode == 1 && d->stride == 2 && d->R == 3 && d->S == 3 && d->pad == 1 && !d->aniso && d->out_sp <= 1 &&
-      d->Ho == 2 * d->Hs && d->Wo == 2 * d->Ws && d->C % 64 == 0 && d->ldc >= d->Nc && !(e && (e->dropout_p > 0.f || e->sigmoid))) {
-    int rc = validate(d, dtype, "td_conv_gemm");
-    if (rc) return rc;
-    return conv_dgrad_s2_by_parity(src, wmat, out, d, e, dtype, stream);
+typedef void (*GemmKernel)(GemmParams);
+typedef void (*PersistentKernel)(GemmParams, int, int);
+template <typename T, int BM, int BN, int NST>
+static GemmKernel tiled_instance(int walk) {
+  switch (walk) {
+    case TD_GEMM_WALK_POINTWISE: return conv_gemm_kernel<T, BM, BN, NST, true>;
+    case TD_GEMM_WALK_TAP_UNIFORM: return conv_gemm_kernel<T, BM, BN, NST, false, true>;
+    case TD_GEMM_WALK_GATHER: return conv_gemm_kernel<T, BM, BN, NST, false>;
+    default: return conv_gemm_kernel<T, BM, BN, 2, true, false, true>;  // td_linear_ex: two stages on every tile
   }
-  return conv_gemm_launch(src, wmat, out, d, e, dtype, stream, nullptr);
+}
+template <int NKT>
+static PersistentKernel persistent_instance(bool res, bool msk) {
+  if (res) return msk ? pw_resident2_kernel<NKT, true, true> : pw_resident2_kernel<NKT, true, false>;
+  return msk ? pw_resident2_kernel<NKT, false, true> : pw_resident2_kernel<NKT, false, false>;
 }
 
-static int conv_gemm_launch(const void* src, const void* wmat, void* out, const td_conv_desc* d, const td_epilogue* e, int dtype,
-                            td_stream_t stream, const WeightSubset* sub) {
-  TD_REQUIRE(src && wmat && out && d, "td_conv_gemm: null pointer");
-  int rc = validate(d, dtype, "td_conv_gemm");
+// maps a route to its kernel instance and launches it, with the profiler's record around the launch
+static int launch_route(const GemmRoute& r, GemmParams& p, hipStream_t st) {
+  const bool bf16 = r.dtype == TD_BF16, tu = r.walk == TD_GEMM_WALK_TAP_UNIFORM;
+  GemmKernel k = nullptr;
+  PersistentKernel kp = nullptr;
+  switch (r.kernel) {
+    case TD_GEMM_KERNEL_PERSISTENT:
+      kp = r.nkt == 1 ? persistent_instance<1>(r.res, r.msk) : r.nkt == 2 ? persistent_instance<2>(r.res, r.msk) :
+           r.nkt == 3 ? persistent_instance<3>(r.res, r.msk) : persistent_instance<4>(r.res, r.msk);
+      break;
+    case TD_GEMM_KERNEL_BIG8:
+      if (tu) k = r.res ? conv_gemm_big8_kernel<true, true> : conv_gemm_big8_kernel<true, false>;
+      else k = r.res ? conv_gemm_big8_kernel<false, true> : conv_gemm_big8_kernel<false, false>;
+      break;
+    case TD_GEMM_KERNEL_BIG8N: k = tu ? conv_gemm_big8n_kernel<true> : conv_gemm_big8n_kernel<false>; break;
+    default:
+      if (r.bn == 64) k = bf16 ? tiled_instance<u16, 128, 64, 2>(r.walk) : tiled_instance<float, 128, 64, 2>(r.walk);
+      else if (r.stages == 3) k = tiled_instance<u16, 64, 128, 3>(r.walk);
+      else if (r.bm == 64) k = bf16 ? tiled_instance<u16, 64, 128, 2>(r.walk) : tiled_instance<float, 64, 128, 2>(r.walk);
+      else k = bf16 ? tiled_instance<u16, 128, 128, 2>(r.walk) : tiled_instance<float, 128, 128, 2>(r.walk);
+  }
+  const bool prof = prof_on();
+  if (prof) {
+    prof_begin(r.family, r.dtype, 2.0 * r.M * r.N * r.K, st, r.M, r.N, r.K, r.R, r.stride, r.mode);
+    prof_set_bytes(r.bytes);
+  }
+  if (kp) kp<<<r.grid, r.block, 0, st>>>(p, r.MTp, r.Pp);
+  else k<<<r.grid, r.block, 0, st>>>(p);
+  if (prof) prof_end(st);
+  return check_launch(r.label);
+}
+
+// one launch of td_conv_gemm: plan it, then launch it - or, for the query, hand the plan back (no pointer is used, no device touched)
+static int conv_gemm_launch(const void* src, const void* wmat, void* out, const td_conv_desc* d, const td_epilogue* e, int dtype, int n_cu,
+                            const WeightSubset* sub, td_stream_t stream, td_gemm_route* report) {
+  GemmRoute r;
+  int rc = plan_conv_launch(d, epi_flags(e), dtype, n_cu, gemm_knobs(), sub, r);
   if (rc) return rc;
   GemmParams p;
   memset(&p, 0, sizeof(p));
+  rc = fill_epilogue(p, e, "td_conv_gemm");
+  if (rc) return rc;
+  if (report) {
+    *report = r;
+    return TD_OK;
+  }
   p.src = (const char*)src;
   p.w = (const char*)wmat;
   p.out = (char*)out;
   p.d = *d;
   if (p.d.out_sp < 1) p.d.out_sp = 1;
-  p.M = d->N * d->Ho * d->Wo;
-  p.K = d->R * d->S * d->C;
-  {
-    const double es = dtype == TD_BF16 ? 2.0 : 4.0;
-    const double sb = (double)d->N * d->Hs * d->Ws * d->C * es, wb = (double)d->Nc * p.K * es;
-    TD_REQUIRE(sb < 4294967000.0 && wb < 4294967000.0, "td_conv_gemm: operand exceeds the 4 GiB buffer-descriptor range");
-    p.src_bytes = (uint32_t)sb;
-    p.w_bytes = (uint32_t)wb;
-  }
+  p.M = r.M;
+  p.K = r.K;
+  p.src_bytes = r.src_bytes;
+  p.w_bytes = r.w_bytes;
   if (sub) {
     p.w_ld = sub->w_ld;
-    p.w_bytes = (uint32_t)sub->w_bytes;
     p.use_wtap = sub->ntap > 1;
     for (int i = 0; i < 4; ++i) p.wtap[i] = sub->wtap[i];
   }
-  p.alpha = 1.f;
+  p.tap_inner = r.tap_inner;
   p.dbg = g_dbg;
-  if (e) {
-    p.bias = e->bias;
-    p.residual = (const char*)e->residual;
-    p.mask_src = (const char*)e->mask_src;
-    p.relu = e->relu;
-    p.sigmoid = e->sigmoid;
-    if (e->alpha != 0.f) p.alpha = e->alpha;
-    if (e->dropout_p > 0.f) {
-      TD_REQUIRE(e->dropout_p < 1.f, "td_conv_gemm: dropout_p must be < 1");
-      p.drop_thresh = (uint32_t)((double)e->dropout_p * 4294967296.0);
-      if (p.drop_thresh == 0) p.drop_thresh = 1;
-      p.drop_scale = 1.f / (1.f - e->dropout_p);
-      p.seed = e->dropout_seed;
-      p.seed_dev = e->dropout_counter;
-    }
+  return launch_route(r, p, (hipStream_t)stream);
+}
+
+// the whole call: one launch, or the four parity classes of a stride-2 3x3 input gradient (gemm_route.h)
+static int conv_gemm_call(const void* src, const void* wmat, void* out, const td_conv_desc* d, const td_epilogue* e, int dtype, int n_cu,
+                          td_stream_t stream, td_gemm_route* report, int* n_report) {
+  const bool split = conv_splits_by_parity(d, e, dtype, gemm_knobs());
+  if (n_report) *n_report = split ? 4 : 1;
+  if (!split) return conv_gemm_launch(src, wmat, out, d, e, dtype, n_cu, nullptr, stream, report);
+  int rc = validate(d, dtype, "td_conv_gemm");
+  for (int i = 0; i < 4 && !rc; ++i) {
+    const ParityClass c = parity_class(d, i >> 1, i & 1);
+    td_epilogue ec;
+    memset(&ec, 0, sizeof(ec));
+    if (e) ec = *e;
+    if (ec.residual) ec.residual = (const char*)ec.residual + c.out_off;
+    if (ec.mask_src) ec.mask_src = (const char*)ec.mask_src + c.out_off;
+    if (report) rc = conv_gemm_launch(nullptr, nullptr, nullptr, &c.d, &ec, dtype, n_cu, &c.sub, stream, report + i);
+    else rc = conv_gemm_launch(src, (const char*)wmat + c.w_off, (char*)out + c.out_off, &c.d, &ec, dtype, n_cu, &c.sub, stream, nullptr);
   }
-  TD_REQUIRE(d->ldc >= d->Nc, "td_conv_gemm: ldc < Nc");
-  hipStream_t st = (hipStream_t)stream;
-  static const int n_cu = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-  }();
-  {
-    // persistent weight-stationary instance (see pw_resident2_kernel): bf16 pointwise layers with short K and many rows
-    static const int persist = [] { const char* e_ = getenv("TD_PW_PERSIST"); return e_ ? atoi(e_) : 1; }();
-    static const int persist_dropout = [] { const char* e_ = getenv("TD_PW_PERSIST_DROPOUT"); return e_ ? atoi(e_) : 1; }();  // (A/B: 0 = dropout epilogues on the tiled kernel)
-    // dense rows, or the strided 1x1 of a downsample branch in forward geometry (the kernel derives the source pixel per row)
-    const bool pw0 = d->R == 1 && d->S == 1 && d->pad == 0 && p.d.out_sp == 1 && !d->aniso &&
-                     ((d->stride == 1 && d->Hs == d->Ho && d->Ws == d->Wo) ||
-                      (d->stride > 1 && d->mode == 0 && (d->Ho - 1) * d->stride < d->Hs && (d->Wo - 1) * d->stride < d->Ws));
-    const int NTp = d->Nc / 128, Pp = 2 * n_cu / 8;
-    const bool shape_ok = pw0 && !p.w_ld && dtype == TD_BF16 && p.K % 64 == 0 && p.K <= 256 && d->Nc % 128 == 0 &&
-                          (NTp == 1 || NTp == 2 || NTp == 4 || NTp == 8 || NTp == 16) && Pp >= NTp && d->ldc % 8 == 0 && !p.sigmoid &&
-                          p.alpha == 1.f && n_cu % 8 == 0 && (!p.drop_thresh || persist_dropout) && (double)p.M * d->ldc < 2147483000.0;
-    const int MTp = cdiv(p.M, 64);
-    const int groups = shape_ok ? 8 * (Pp / NTp) : 1;
-    if (persist && shape_ok && MTp >= persist_min_tiles() * groups && !(persist == 2 && p.mask_src) && !(persist == 3 && d->mode != 0)) {
-      const bool prof_ = prof_on();
-      if (prof_) {
-        prof_begin(TD_PROF_PW_RESIDENT, dtype, 2.0 * p.M * d->Nc * p.K, st, p.M, d->Nc, p.K, d->R, d->stride, d->mode);
-        const double es_ = 2.0;
-        double by = ((double)p.M * p.K + (double)d->Nc * p.K + (double)p.M * d->Nc) * es_;
-        if (p.residual) by += (double)p.M * d->Nc * es_;
-        if (p.mask_src) by += (double)p.M * d->Nc * es_;
-        prof_set_bytes(by);
-      }
-      const int nkt = p.K / 64;
-      const bool hr = p.residual != nullptr, hm = p.mask_src != nullptr;
-      dim3 g2(2 * n_cu);  // two resident workgroups per CU (64 KiB of LDS each)
-#define TD_PWR(NK)                                                                               \
-  do {                                                                                           \
-    if (hr && hm) pw_resident2_kernel<NK, true, true><<<g2, 256, 0, st>>>(p, MTp, Pp);          \
-    else if (hr) pw_resident2_kernel<NK, true, false><<<g2, 256, 0, st>>>(p, MTp, Pp);          \
-    else if (hm) pw_resident2_kernel<NK, false, true><<<g2, 256, 0, st>>>(p, MTp, Pp);          \
-    else pw_resident2_kernel<NK, false, false><<<g2, 256, 0, st>>>(p, MTp, Pp);                 \
-  } while (0)
-      if (nkt == 1) TD_PWR(1);
-      else if (nkt == 2) TD_PWR(2);
-      else if (nkt == 3) TD_PWR(3);
-      else TD_PWR(4);
-#undef TD_PWR
-      if (prof_) prof_end(st);
-      return check_launch("td_conv_gemm(pw_resident)");
-    }
-  }
-  // tile choice: 128x64 for <=64 output channels; 64x128 when 128x128 would leave the 256 CUs under-filled
-  const bool narrow = d->Nc <= 64;
-  const int tiles128 = cdiv(p.M, 128) * cdiv(d->Nc, 128);
-  // 64x128 (3 workgroups / CU) also for the short-K, HBM-bound 1x1 layers: more loads in flight per CU
-  const bool small_m = !narrow && (tiles128 < 512 || p.K <= 512);
-  const int BMsel = small_m ? 64 : 128, BNsel = narrow ? 64 : 128;
-  const int MT = cdiv(p.M, BMsel), NTl = cdiv(d->Nc, BNsel);
-  dim3 grid(8 * cdiv(MT, 8) * NTl);
-  const bool prof = prof_on();
-  const bool pw = d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0 && p.d.out_sp == 1 && d->Hs == d->Ho && d->Ws == d->Wo;
-  // tap-uniform addressing (see conv_gemm_kernel): spatial convs whose channel count is a multiple of the K tile
-  static const int tu_on = [] { const char* e_ = getenv("TD_CONV_TAP_UNIFORM"); return e_ ? atoi(e_) : 1; }();
-  const int bk = dtype == TD_BF16 ? 64 : 32;
-  // (a strided 1x1 - the downsample branch of a stage's first block - is the one-tap case of the same addressing)
-  const bool tu = (tu_on || p.use_wtap) && !pw && !d->aniso && (d->R * d->S > 1 || (d->stride > 1 && d->mode == 0)) && d->R * d->S <= 32 && d->C % bk == 0 &&
-                  (p.d.out_sp == 1 || d->mode == 0) && (d->mode == 0 || d->stride == 1);
-  // a tap -> column-block map (WeightSubset: the parity classes of a stride-2 input gradient) is honoured by the tap-uniform K walk only
-  TD_REQUIRE(tu || !p.use_wtap, "td_conv_gemm: a weight-column subset needs the tap-uniform addressing (C %% %d == 0, at most 32 taps)", bk);
-  {
-    // 256-row tiles (conv_gemm_big8_kernel / conv_gemm_big8n_kernel): MFMA-bound bf16 layers with enough workgroups to matter
-    static const int big_on = [] { const char* e_ = getenv("TD_CONV_BIG"); return e_ ? atoi(e_) : 1; }();
-    static const int big_min = [] { const char* e_ = getenv("TD_CONV_BIG_MIN_WG"); return e_ ? atoi(e_) : 160; }();
-    const int bnb = d->Nc % 256 == 0 ? 256 : 128;
-    const int wgs = cdiv(p.M, 256) * (d->Nc / bnb);
-    if (big_on && dtype == TD_BF16 && (pw || tu) && p.d.out_sp == 1 && !p.use_wtap && !p.w_ld && d->Nc % 128 == 0 && p.K % 64 == 0 && p.K >= 512 && d->ldc % 8 == 0 && !p.sigmoid &&
-        !p.drop_thresh && wgs >= big_min && (double)p.M * d->ldc < 2147483000.0 &&  // (rows past M leave through an out-of-range offset: the tensor must end below it)
-        p.K <= 64 * 154 && p.M < (1 << 24)) {  // (the K table's 160 entries; rows decoded with float reciprocals.  Anything larger runs on 128 x 128 tiles)
-      if (prof) {
-        prof_begin(tu ? TD_PROF_GEMM_256 : TD_PROF_GEMM_256_PW, dtype, 2.0 * p.M * d->Nc * p.K, st, p.M, d->Nc, p.K, d->R, d->stride, d->mode);
-        double by = ((double)d->N * d->Hs * d->Ws * d->C + (double)d->Nc * p.K + (double)p.M * d->Nc) * 2.0;
-        if (p.residual) by += (double)p.M * d->Nc * 2.0;
-        if (p.mask_src) by += (double)p.M * d->Nc * 2.0;
-        prof_set_bytes(by);
-      }
-      static const int tap_inner = [] { const char* e_ = getenv("TD_CONV_TAP_INNER"); return e_ ? atoi(e_) : 1; }();
-      p.tap_inner = tu && tap_inner && d->R * d->S > 1;
-      dim3 gb(8 * cdiv(cdiv(p.M, 256), 8) * (d->Nc / bnb));
-      static const int persist8 = [] { const char* e_ = getenv("TD_CONV_BIG_PERSIST"); return e_ ? atoi(e_) : 1; }();  // (A/B: 0 = one workgroup per tile)
-      if (bnb == 256) {
-        const dim3 gp(persist8 && n_cu % 8 == 0 ? std::min((unsigned)n_cu, gb.x) : gb.x);
-        if (tu && p.residual) conv_gemm_big8_kernel<true, true><<<gp, 512, 0, st>>>(p);
-        else if (tu) conv_gemm_big8_kernel<true, false><<<gp, 512, 0, st>>>(p);
-        else if (p.residual) conv_gemm_big8_kernel<false, true><<<gp, 512, 0, st>>>(p);
-        else conv_gemm_big8_kernel<false, false><<<gp, 512, 0, st>>>(p);
-      } else {
-        if (tu) conv_gemm_big8n_kernel<true><<<gb, 512, 0, st>>>(p);
-        else conv_gemm_big8n_kernel<false><<<gb, 512, 0, st>>>(p);
-      }
-      if (prof) prof_end(st);
-      return check_launch("td_conv_gemm(256-row tiles)");
-    }
-  }
-  if (prof) prof_begin(narrow ? TD_PROF_GEMM_128x64 : (small_m ? TD_PROF_GEMM_64x128 : TD_PROF_GEMM_128x128), dtype, 2.0 * p.M * d->Nc * p.K, st, p.M, d->Nc, p.K, d->R, d->stride, d->mode);
-  if (prof) {
-    // algorithmic HBM bytes: every operand / result tensor once (the gathered source counted as the tensor it is read from)
-    const double es = dtype == TD_BF16 ? 2.0 : 4.0;
-    const double rows_out = d->out_sp > 1 ? (double)d->N * d->out_H * d->out_W : (double)p.M;
-    double by = ((double)d->N * d->Hs * d->Ws * d->C + (double)d->Nc * p.K + (double)p.M * d->Nc) * es;
-    if (e && e->residual) by += rows_out * d->Nc * es;
-    if (e && e->mask_src) by += rows_out * d->Nc * es;
-    prof_set_bytes(by);
-  }
-#define TD_LAUNCH(TT, BMv, BNv)                                                                   \
-  do {                                                                                            \
-    if (pw) conv_gemm_kernel<TT, BMv, BNv, 2, true><<<grid, 256, 0, st>>>(p);                    \
-    else if (tu) conv_gemm_kernel<TT, BMv, BNv, 2, false, true><<<grid, 256, 0, st>>>(p);        \
-    else conv_gemm_kernel<TT, BMv, BNv, 2, false><<<grid, 256, 0, st>>>(p);                      \
-  } while (0)
-  static const int deep = [] { const char* e_ = getenv("TD_CONV_DEEP"); return e_ ? atoi(e_) : 1; }();
-  // under-filled launch (at most two 64x128 workgroups per CU anyway) with a long K loop: the third stage costs nothing
-  // in occupancy and halves the exposed DMA round trips
-  const bool deep_ok = deep && small_m && (int)grid.x <= 2 * 256 && p.K >= 1024;  // measured: +6 % at K >= 1024, neutral-to-negative at K = 256
-  if (dtype == TD_BF16) {
-    if (narrow) TD_LAUNCH(u16, 128, 64);
-    else if (deep_ok && pw) conv_gemm_kernel<u16, 64, 128, 3, true><<<grid, 256, 0, st>>>(p);
-    else if (deep_ok && tu) conv_gemm_kernel<u16, 64, 128, 3, false, true><<<grid, 256, 0, st>>>(p);
-    else if (deep_ok) conv_gemm_kernel<u16, 64, 128, 3, false><<<grid, 256, 0, st>>>(p);
-    else if (small_m) TD_LAUNCH(u16, 64, 128);
-    else TD_LAUNCH(u16, 128, 128);
-  } else {
-    if (narrow) TD_LAUNCH(float, 128, 64);
-    else if (small_m) TD_LAUNCH(float, 64, 128);
-    else TD_LAUNCH(float, 128, 128);
-  }
-#undef TD_LAUNCH
-  if (prof) prof_end(st);
-  return check_launch("td_conv_gemm");
+  return rc;
+}
+
+extern "C" int td_conv_gemm(const void* src, const void* wmat, void* out, const td_conv_desc* d, const td_epilogue* e,
+                            int dtype, td_stream_t stream) {
+  TD_REQUIRE(src && wmat && out && d, "td_conv_gemm: null pointer");
+  return conv_gemm_call(src, wmat, out, d, e, dtype, cu_count(), stream, nullptr, nullptr);
+}
+
+extern "C" int td_conv_gemm_route(const td_conv_desc* d, const td_epilogue* e, int dtype, int n_cu, td_gemm_route* routes, int* n_routes) {
+  TD_REQUIRE(d && routes && n_routes, "td_conv_gemm: null pointer");
+  TD_REQUIRE(n_cu >= 1, "td_conv_gemm_route: n_cu=%d", n_cu);
+  return conv_gemm_call(nullptr, nullptr, nullptr, d, e, dtype, n_cu, nullptr, routes, n_routes);
 }
 
 // out[out_map[m]][n] = epilogue( [A1[a1_map[m]] | A2[a2_map[m]]] @ wmat[n][K1 + K2]^T (+ residual[res_map[m]][n]) )
-extern "C" int td_linear_ex(const void* a1, const void* a2, const void* wmat, void* out, const td_linear_ex_desc* x, const td_epilogue* e,
-                            int dtype, td_stream_t stream) {
-  TD_REQUIRE(a1 && wmat && out && x, "td_linear_ex: null pointer");
-  TD_REQUIRE(dtype == TD_F32 || dtype == TD_BF16, "td_linear_ex: bad dtype %d", dtype);
-  const int vec = dtype == TD_BF16 ? 8 : 4, bk = dtype == TD_BF16 ? 64 : 32;
-  const int es = dtype == TD_BF16 ? 2 : 4;
-  const int K2 = a2 ? x->K2 : 0;
-  TD_REQUIRE(x->M >= 1 && x->N >= 1 && x->K1 >= vec && K2 >= 0, "td_linear_ex: bad sizes");
-  TD_REQUIRE(x->K1 % vec == 0 && K2 % vec == 0 && x->lda1 % vec == 0 && (!a2 || x->lda2 % vec == 0), "td_linear_ex: K1 / K2 / lda must be multiples of %d", vec);
-  TD_REQUIRE(!a2 || x->K1 % bk == 0, "td_linear_ex: with a second source K1=%d must be a multiple of the K tile (%d)", x->K1, bk);
-  TD_REQUIRE(x->lda1 >= x->K1 && (!a2 || x->lda2 >= K2) && x->ldc >= x->N, "td_linear_ex: row stride smaller than the row");
-  TD_REQUIRE(x->rows1 >= 1 && (!a2 || x->rows2 >= 1) && (x->a1_map || x->rows1 >= x->M) && (!a2 || x->a2_map || x->rows2 >= x->M),
-             "td_linear_ex: source has fewer rows than M and no row map");
+static int linear_ex_call(const void* a1, const void* a2, const void* wmat, void* out, const td_linear_ex_desc* x, bool has_a2, const td_epilogue* e,
+                          int dtype, td_stream_t stream, td_gemm_route* report) {
+  GemmRoute r;
+  int rc = plan_linear_ex(x, has_a2, epi_flags(e), dtype, r);
+  if (rc) return rc;
   GemmParams p;
   memset(&p, 0, sizeof(p));
+  rc = fill_epilogue(p, e, "td_linear_ex");
+  if (rc) return rc;
+  if (report) {
+    *report = r;
+    return TD_OK;
+  }
   p.src = (const char*)a1;
   p.src2 = (const char*)a2;
   p.w = (const char*)wmat;
   p.out = (char*)out;
-  p.M = x->M;
-  p.K = x->K1 + K2;
+  p.M = r.M;
+  p.K = r.K;
   p.K1 = x->K1;
   p.lda1 = x->lda1;
   p.lda2 = a2 ? x->lda2 : 0;
   p.ldr = x->ldr > 0 ? x->ldr : x->ldc;
   p.w_shared = (a2 && x->w_shared) ? 1 : 0;
-  TD_REQUIRE(!p.w_shared || K2 == x->K1, "td_linear_ex: a shared weight needs K2 == K1");
   p.a1_map = x->a1_map;
   p.a2_map = a2 ? x->a2_map : nullptr;
   p.out_map = x->out_map;
   p.res_map = x->res_map;
-  td_conv_desc d;
-  memset(&d, 0, sizeof(d));
-  d.N = 1; d.Hs = x->M; d.Ws = 1; d.C = p.K; d.Ho = x->M; d.Wo = 1; d.R = d.S = 1; d.stride = 1; d.Nc = x->N; d.ldc = x->ldc; d.out_sp = 1;
-  p.d = d;
-  {
-    const double b1 = (double)x->rows1 * x->lda1 * es, b2 = a2 ? (double)x->rows2 * x->lda2 * es : 16.0, wb = (double)x->N * (p.w_shared ? x->K1 : p.K) * es;
-    TD_REQUIRE(b1 < 4294967000.0 && b2 < 4294967000.0 && wb < 4294967000.0, "td_linear_ex: operand exceeds the 4 GiB buffer-descriptor range");
-    p.src_bytes = (uint32_t)b1;
-    p.src2_bytes = (uint32_t)b2;
-    p.w_bytes = (uint32_t)wb;
-  }
-  p.alpha = 1.f;
-  if (e) {
-    p.bias = e->bias;
-    p.residual = (const char*)e->residual;
-    p.mask_src = (const char*)e->mask_src;
-    p.relu = e->relu;
-    p.sigmoid = e->sigmoid;
-    if (e->alpha != 0.f) p.alpha = e->alpha;
-    if (e->dropout_p > 0.f) {
-      TD_REQUIRE(e->dropout_p < 1.f, "td_linear_ex: dropout_p must be < 1");
-      p.drop_thresh = (uint32_t)((double)e->dropout_p * 4294967296.0);
-      if (p.drop_thresh == 0) p.drop_thresh = 1;
-      p.drop_scale = 1.f / (1.f - e->dropout_p);
-      p.seed = e->dropout_seed;
-      p.seed_dev = e->dropout_counter;
-    }
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const bool narrow = x->N <= 64;
-  const int tiles128 = cdiv(p.M, 128) * cdiv(x->N, 128);
-  const bool small_m = !narrow && (tiles128 < 512 || p.K <= 512);
-  const int BMsel = small_m ? 64 : 128, BNsel = narrow ? 64 : 128;
-  dim3 grid(8 * cdiv(cdiv(p.M, BMsel), 8) * cdiv(x->N, BNsel));
-  const bool prof = prof_on();
-  if (prof) {
-    prof_begin(narrow ? TD_PROF_GEMM_128x64 : (small_m ? TD_PROF_GEMM_64x128 : TD_PROF_GEMM_128x128), dtype, 2.0 * p.M * x->N * p.K, st, p.M, x->N, p.K, 1, 1, 2);
-    double by = ((double)p.M * p.K + (double)x->N * p.K + (double)p.M * x->N) * es;  // every gathered row counted once per use
-    if (p.residual) by += (double)p.M * x->N * es;
-    if (p.mask_src) by += (double)p.M * x->N * es;
-    prof_set_bytes(by);
-  }
-#define TD_LX(TT)                                                                                     \
-  do {                                                                                                \
-    if (narrow) conv_gemm_kernel<TT, 128, 64, 2, true, false, true><<<grid, 256, 0, st>>>(p);         \
-    else if (small_m) conv_gemm_kernel<TT, 64, 128, 2, true, false, true><<<grid, 256, 0, st>>>(p);   \
-    else conv_gemm_kernel<TT, 128, 128, 2, true, false, true><<<grid, 256, 0, st>>>(p);               \
-  } while (0)
-  if (dtype == TD_BF16) TD_LX(u16);
-  else TD_LX(float);
-#undef TD_LX
-  if (prof) prof_end(st);
-  return check_launch("td_linear_ex");
+  p.d.N = 1; p.d.Hs = x->M; p.d.Ws = 1; p.d.C = p.K; p.d.Ho = x->M; p.d.Wo = 1; p.d.R = p.d.S = 1; p.d.stride = 1; p.d.Nc = x->N; p.d.ldc = x->ldc; p.d.out_sp = 1;
+  p.src_bytes = r.src_bytes;
+  p.src2_bytes = r.src2_bytes;
+  p.w_bytes = r.w_bytes;
+  return launch_route(r, p, (hipStream_t)stream);
 }
+
+extern "C" int td_linear_ex(const void* a1, const void* a2, const void* wmat, void* out, const td_linear_ex_desc* x, const td_epilogue* e,
+                            int dtype, td_stream_t stream) {
+  TD_REQUIRE(a1 && wmat && out && x, "td_linear_ex: null pointer");
+  return linear_ex_call(a1, a2, wmat, out, x, a2 != nullptr, e, dtype, stream, nullptr);
+}
+
+extern "C" int td_linear_ex_route(const td_linear_ex_desc* x, int has_a2, const td_epilogue* e, int dtype, int n_cu, td_gemm_route* routes, int* n_routes) {
+  TD_REQUIRE(x && routes && n_routes, "td_linear_ex: null pointer");
+  (void)n_cu;  // td_linear_ex's tile rule does not read the CU count
+  *n_routes = 1;
+  return linear_ex_call(nullptr, nullptr, nullptr, nullptr, x, has_a2 != 0, e, dtype, nullptr, routes);
+}
+
 
 // fills everything of p except the output fields; returns the split count through *splits_io.
 // auto_mode: 0 = single launch (about one workgroup per CU), > 0 = batched launch with work items of that many stages
@@ -2441,7 +2298,7 @@ static int wgrad_fill(WgradParams& p, const void* g, const void* src, const td_c
     if (auto_mode == 0) {
       // single launch: about one workgroup per CU (TD_WGRAD_BLOCKS, default 256), at least 8 reduction stages per split.
       // measured: 192-256 workgroups beat 512-1536 (fewer fp32 atomics per output tile)
-      static const int target_blocks = [] { const char* e = getenv("TD_WGRAD_BLOCKS"); return e ? atoi(e) : 256; }();
+      const int target_blocks = gemm_knobs().wgrad_blocks;
       const int tiles = p.tn * p.tk;
       splits = target_blocks / tiles;  // four stages take one workgroup per CU: never a second round
       const int maxs = cdiv(p.M, 8 * mk);
@@ -2525,17 +2382,11 @@ static int wgrad_batch_phase(const td_wgrad_job* jobs, int n_jobs, int dtype, vo
   hipStream_t st = (hipStream_t)stream;
   std::vector<WgradParams> tab[3];  // [0] general geometry, [1] pointwise, [2] wide tiles (conv_wgrad_wide_batch_kernel)
   double flops = 0, abytes = 0;
-  static const int wide_on = [] { const char* e = getenv("TD_WGRAD_WIDE"); return e ? atoi(e) : 1; }();
-  static const int wide_min_m = [] { const char* e = getenv("TD_WGRAD_WIDE_MIN_M"); return e ? atoi(e) : 4096; }();
+  const int wide_on = gemm_knobs().wgrad_wide, wide_min_m = gemm_knobs().wgrad_wide_min_m;
   // stages (64 / 32 reduction rows) per work item: total work of the launch in 256 x 256 tile-stages / (3.4 items per CU)
   int item_stages;
   {
-    static const int fixed = [] { const char* e = getenv("TD_WGRAD_SPLIT_STAGES"); return e ? atoi(e) : 0; }();
-    static const int n_cu = [] {
-      int dev = 0, cus = 256;
-      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      return cus;
-    }();
+    const int fixed = gemm_knobs().wgrad_split_stages, n_cu = cu_count();
     double units = 0;
     const int mk = dtype == TD_BF16 ? 64 : 32;
     for (int i = 0; i < n_jobs; ++i) {

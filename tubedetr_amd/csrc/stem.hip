@@ -215,11 +215,7 @@ extern "C" int td_stem_pool(const void* x_pairs, const void* w_pairs, const floa
   p.CW = (W + 6 - 7) / 2 + 1;
   p.PH = (p.CH + 2 - 3) / 2 + 1;
   p.PW = (p.CW + 2 - 3) / 2 + 1;
-  static const int n_cu = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus;
-  }();
+  const int n_cu = cu_count();
   hipStream_t st = (hipStream_t)stream;
   const bool prof = prof_on();
   if (prof) {

@@ -54,6 +54,17 @@ void prof_set_bytes(double algorithmic_bytes);  // of the launch recorded by the
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// CU count of the current device, read once per process (api.cpp); 256 when no device answers
+int cu_count();
+
+// dropout threshold of every dropout-capable entry point: an element is dropped when its 32-bit hash is below p * 2^32
+// (a positive p never rounds down to "keep everything").  The callers check p < 1 themselves.
+inline uint32_t dropout_threshold(float p) {
+  if (!(p > 0.f)) return 0u;
+  const uint32_t t = (uint32_t)((double)p * 4294967296.0);
+  return t ? t : 1u;
+}
+
 // ---- bf16 <-> f32 (round-to-nearest-even), bit exact with torch's float->bfloat16 ----
 __device__ __forceinline__ float bf16_to_f32(u16 v) { return __uint_as_float(((uint32_t)v) << 16); }
 __device__ __forceinline__ u16 f32_to_bf16(float f) {

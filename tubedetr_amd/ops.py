@@ -124,6 +124,22 @@ def conv_gemm_raw(src: Tensor, w: Tensor, out: Tensor, desc: ConvDesc, epi: Opti
                                   dtype_code(src.dtype), stream_ptr()), "td_conv_gemm")
 
 
+def _routes(fn, what: str, *args):
+    buf, n = (_hip.GemmRoute * 4)(), C.c_int(0)
+    check(fn(*args, buf, C.byref(n)), what)
+    return [buf[i] for i in range(n.value)]
+
+
+def conv_gemm_route(desc: ConvDesc, epi: Optional[Epilogue], dtype: torch.dtype, n_cu: int):
+    """The launches td_conv_gemm would make for this call on a device of n_cu CUs (one _hip.GemmRoute each; no device is touched)."""
+    return _routes(_hip.lib().td_conv_gemm_route, "td_conv_gemm_route", C.byref(desc), C.byref(epi) if epi is not None else None, dtype_code(dtype), n_cu)
+
+
+def linear_ex_route(x: "_hip.LinearExDesc", has_a2: bool, epi: Optional[Epilogue], dtype: torch.dtype, n_cu: int):
+    """The launch td_linear_ex would make for this call."""
+    return _routes(_hip.lib().td_linear_ex_route, "td_linear_ex_route", C.byref(x), int(has_a2), C.byref(epi) if epi is not None else None, dtype_code(dtype), n_cu)
+
+
 def conv_fwd(x: Tensor, w_fwd: Tensor, bias: Optional[Tensor], R: int, S: int, stride: int, pad: int, *,
              residual: Optional[Tensor] = None, relu: bool = False, out: Optional[Tensor] = None) -> Tensor:
     """x [N,H,W,C] (NHWC), w_fwd [Co, R*S*C]  ->  y [N,Ho,Wo,Co] = relu(conv(x) + bias + residual)."""
@@ -324,6 +340,14 @@ def linear_ex(a1: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, a2: Optio
     if out is None:
         out = torch.empty((out_rows if out_rows is not None else M, Nn), dtype=a1.dtype, device=a1.device)
     _rows2d(out)
+    x = linear_ex_desc(M, Nn, K1, K2, a1, a2, out, residual, w_shared, a1_map, a2_map, out_map, res_map)
+    epi = _epi(bias, residual, mask_src, relu, False, dropout_p, seed, alpha)
+    check(_hip.lib().td_linear_ex(ptr(a1), ptr(a2), ptr(w), ptr(out), C.byref(x), C.byref(epi), dtype_code(a1.dtype), stream_ptr()), "td_linear_ex")
+    return out
+
+
+def linear_ex_desc(M, Nn, K1, K2, a1, a2, out, residual, w_shared, a1_map, a2_map, out_map, res_map) -> "_hip.LinearExDesc":
+    """td_linear_ex_desc of a linear_ex call (also what linear_ex_route takes)."""
     x = _hip.LinearExDesc()
     x.M, x.N, x.K1, x.K2 = M, Nn, K1, K2
     x.lda1, x.lda2, x.ldc = a1.stride(0), (a2.stride(0) if a2 is not None else 0), out.stride(0)
@@ -331,9 +355,7 @@ def linear_ex(a1: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, a2: Optio
     x.w_shared = int(bool(w_shared and a2 is not None))
     x.rows1, x.rows2 = a1.shape[0], (a2.shape[0] if a2 is not None else 0)
     x.a1_map, x.a2_map, x.out_map, x.res_map = ptr(a1_map), ptr(a2_map), ptr(out_map), ptr(res_map)
-    epi = _epi(bias, residual, mask_src, relu, False, dropout_p, seed, alpha)
-    check(_hip.lib().td_linear_ex(ptr(a1), ptr(a2), ptr(w), ptr(out), C.byref(x), C.byref(epi), dtype_code(a1.dtype), stream_ptr()), "td_linear_ex")
-    return out
+    return x
 
 
 def rows_copy(src: Tensor, src_map: Optional[Tensor], dst: Tensor, dst_map: Optional[Tensor], n_rows: int, add: Optional[Tensor] = None) -> Tensor:
