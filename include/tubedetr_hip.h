@@ -833,6 +833,89 @@ typedef struct td_crop_job {
 size_t td_tube_crop_table_bytes(int n_jobs);
 int td_tube_crop(const td_crop_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
 
+/* ---- Grounded tubes redacted in decoded frames (an addition WITHIN ABI 11: nothing above changed) ----------------------
+ * Hides the answer to a grounding question - or everything but the answer - in the decoded frames of many clips in ONE
+ * launch, in the frames' own pixel format: "blur the man in the red jacket", "pixelate the plate the caption describes",
+ * or the inverse (a spotlight, bystander privacy).  One job takes the UNION of up to eight tubes.  Per job:
+ *   Frames.  Source (src0..2, src_frame_stride, src_pitch0..2) and destination (dst0..2, dst_frame_stride, dst_pitch0..2),
+ *     fmt, T, sh, sw exactly as in td_overlay_job: odd sizes are legal, chroma planes are (sh + 1) / 2 x (sw + 1) / 2.  A
+ *     destination plane may BE its source plane (same pointer, pitch and frame stride: in place); any other overlap of a
+ *     destination plane with a source plane is an error.
+ *   Tube.  Device pointers boxes (fp32 [n_tube][K][4], xyxy in source pixels, required), span (int64 [K][2], nullable:
+ *     first and last tube row of rectangle k, both inclusive) and frame_map (int32 [T], nullable); n_tube; K in 1..8
+ *     rectangles per tube row.
+ *   What to do.  mode = TD_REDACT_FILL / TD_REDACT_MOSAIC / TD_REDACT_BLUR; invert 0 or 1; margin_num / margin_den as in
+ *     td_crop_job; cell (mosaic: even, 2..256); radius (blur: 1..64); color[3] (fill: three bytes IN THE FRAME'S OWN COLOUR
+ *     SPACE, R, G, B or Y, U, V).  The ones the mode does not use are ignored.
+ * The rule (this comment is the specification; exact integers, reproducible to the bit):
+ *   1. Tube row of frame t: r = frame_map ? frame_map[t] : t.
+ *   2. Rectangle k of frame t EXISTS when r is in [0, n_tube), span is NULL or span[k][0] <= r <= span[k][1], all four
+ *      coordinates of boxes[r][k] are finite, and the steps below leave it non-empty.
+ *   3. Rounding is td_tube_overlay's, in fp32: finite values clamped to +-2^20, then x0 = (int)floorf(bx0 + 0.5f), y0, x1, y1
+ *      alike.  Absent if x1 <= x0 or y1 <= y0.
+ *   4. Margin is td_tube_crop's step 4: bw = x1 - x0, bh = y1 - y0; mx = (bw margin_num) / margin_den, my = (bh margin_num) /
+ *      margin_den (integer division); x0 -= mx, x1 += mx, y0 -= my, y1 += my.
+ *   5. Clamp to the frame: wx0 = max(x0, 0), wx1 = min(x1, sw), wy0 = max(y0, 0), wy1 = min(y1, sh).  Absent if wx1 <= wx0
+ *      or wy1 <= wy0.
+ *   6. Snap outward, the same in all three formats, so that the redacted luma set does not depend on the format and every
+ *      existing luma pixel of a 2 x 2 chroma block decides alike.
+ *        FILL and BLUR: X0 = wx0 & ~1, X1 = min(wx1 + (wx1 & 1), sw); Y0, Y1 alike with sh.
+ *        MOSAIC: X0 = (wx0 / cell) cell, X1 = min(((wx1 + cell - 1) / cell) cell, sw); Y0, Y1 alike with sh.  The grid is
+ *        anchored at the frame's origin, not at the box: a moving box does not make the cells crawl.
+ *   7. Selection.  Luma pixel (rgb24: pixel) (y, x) is SELECTED iff (it lies in [X0, X1) x [Y0, Y1) of at least one existing
+ *      rectangle of its frame) XOR invert.  Chroma sample (i, j) is selected iff luma pixel (2 i, 2 j) is.  So a frame without
+ *      a rectangle (r out of range, outside every span, absent boxes) is a plain copy with invert = 0 and selected everywhere
+ *      with invert = 1: nothing is left in the clear by accident.
+ *   8. Values, per plane and per channel (the three channels of rgb24 are independent, and so are the U bytes and the V bytes
+ *      of an NV12 plane).  An unselected byte is the source byte.  A selected byte is
+ *        FILL:   color[0] in the Y plane, color[1] for U, color[2] for V; color[c] for channel c of rgb24.
+ *        MOSAIC: cp = cell (luma, rgb) or cell / 2 (chroma).  The sample's cell is the cp x cp block of the plane's
+ *                origin-anchored grid, cut off at the plane's edge; the value is (sum of the SOURCE samples of the cell +
+ *                n / 2) / n, n the number of samples in the cell.
+ *        BLUR:   rp = radius (luma, rgb) or (radius + 1) / 2 (chroma).  The value is (sum of the SOURCE samples in
+ *                [y - rp, y + rp] x [x - rp, x + rp] that lie in the plane + n / 2) / n, n their count: one exact
+ *                two-dimensional sum, no rounding between a horizontal and a vertical pass.
+ *   9. Every byte of the rows of the job's destination frames gets the value above; no other byte is written (not the row
+ *      padding between the row and the pitch), and no byte outside the source rows is read.
+ *  10. In place is legal for FILL and MOSAIC: a workgroup owns whole cells and reads them before it writes.  BLUR reads
+ *      neighbours that another workgroup may already have rewritten, so BLUR with a destination plane that is its source
+ *      plane is refused with an error that names dst0.
+ * Limits: sides 1..16384; T >= 0; n_tube >= 1; K 1..8; cell even, 2..256 (MOSAIC); radius 1..64 (BLUR); margin_den 1..1024,
+ * margin_num 0..4 margin_den; boxes non-null.  A violation returns an error whose message names the field; nothing is
+ * launched.  `jobs` is a host array consumed before the call returns; the job table lives in caller-provided memory as for
+ * td_tube_overlay (table_host page-locked, table_dev device memory, both of td_tube_redact_table_bytes(n_jobs) bytes).  One
+ * launch for any number of jobs, which may differ in format, mode and size; no allocation, no synchronisation, no atomics. */
+#define TD_REDACT_FILL 0
+#define TD_REDACT_MOSAIC 1
+#define TD_REDACT_BLUR 2
+typedef struct td_redact_job {
+  const void* src0; /* rgb24 pixels, or Y */
+  const void* src1; /* I420: U; NV12: UV pairs; RGB24: ignored */
+  const void* src2; /* I420: V; else ignored */
+  long long src_frame_stride;
+  int src_pitch0, src_pitch1, src_pitch2;
+  void* dst0;
+  void* dst1;
+  void* dst2;
+  long long dst_frame_stride;
+  int dst_pitch0, dst_pitch1, dst_pitch2;
+  int fmt;
+  int T, sh, sw;
+  const float* boxes;
+  const long long* span;
+  const int* frame_map;
+  int n_tube;
+  int K;
+  int mode;
+  int invert;
+  int margin_num, margin_den;
+  int cell;
+  int radius;
+  unsigned char color[3];
+} td_redact_job;
+size_t td_tube_redact_table_bytes(int n_jobs);
+int td_tube_redact(const td_redact_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 /* ---- Which kernel a td_conv_gemm / td_linear_ex call would run on (an addition WITHIN ABI 11: nothing above changed) ----
  * The launching calls plan every launch with one host function and then launch the plan; these two run the same planner and
  * return the plan instead.  They touch no device (no HIP call; the epilogue's pointers are only tested for NULL), use the

@@ -102,6 +102,17 @@ class CropJob(C.Structure):
                [(n, C.c_int) for n in ("n_tube", "oh", "ow", "margin_num", "margin_den", "keep_aspect")] + [(n, C.c_void_p) for n in ("dst", "mask", "valid", "windows")]
 
 
+TD_REDACT_FILL, TD_REDACT_MOSAIC, TD_REDACT_BLUR = 0, 1, 2
+
+
+class RedactJob(C.Structure):
+    """td_redact_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("src0", "src1", "src2")] + [("src_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("src_pitch0", "src_pitch1", "src_pitch2")] + \
+               [(n, C.c_void_p) for n in ("dst0", "dst1", "dst2")] + [("dst_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("dst_pitch0", "dst_pitch1", "dst_pitch2")] + \
+               [(n, C.c_int) for n in ("fmt", "T", "sh", "sw")] + [(n, C.c_void_p) for n in ("boxes", "span", "frame_map")] + \
+               [(n, C.c_int) for n in ("n_tube", "K", "mode", "invert", "margin_num", "margin_den", "cell", "radius")] + [("color", C.c_ubyte * 3)]
+
+
 class ReplicaMapsOut(C.Structure):
     """td_replica_maps_out."""
     _fields_ = [(n, C.c_void_p) for n in ("owner", "vid_of_frame", "vid_of_clip", "query_mask", "frame_dest", "clip_of", "vis_src", "vis_dst", "txt_src", "txt_dst",
@@ -186,6 +197,7 @@ _SIGS = {
     "td_tube_overlay": [C.POINTER(OverlayJob), _I, _P, _P, _SZ, _P],
     "td_sted_topk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "td_tube_crop": [C.POINTER(CropJob), _I, _P, _P, _SZ, _P],
+    "td_tube_redact": [C.POINTER(RedactJob), _I, _P, _P, _SZ, _P],
     "td_conv_gemm_route": [C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_linear_ex_route": [C.POINTER(LinearExDesc), _I, C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
 }
@@ -199,6 +211,7 @@ _SIZE_SIGS = {
     "td_clip_resample_src_table_bytes": [_I],
     "td_tube_overlay_table_bytes": [_I],
     "td_tube_crop_table_bytes": [_I],
+    "td_tube_redact_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],

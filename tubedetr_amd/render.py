@@ -1,5 +1,6 @@
-"""Grounded tubes drawn into decoded frames on the device (td_tube_overlay, csrc/overlay.hip) and cropped out of them
-(td_tube_crop, csrc/tube_crop.hip: ``crop_tubes`` at the end of this file).
+"""Grounded tubes drawn into decoded frames on the device (td_tube_overlay, csrc/overlay.hip), cropped out of them
+(td_tube_crop, csrc/tube_crop.hip: ``crop_tubes``) and hidden in them (td_tube_redact, csrc/redact.hip: ``redact`` at the end
+of this file).
 
 The reference shows an answer on the host: demo_stvg.py:152-194 and server_stvg.py:218-257 re-decode the video to JPEGs,
 open every frame in matplotlib, draw one rectangle and save the JPEG again.  Here the decoded frames stay on the device in
@@ -453,6 +454,153 @@ def crop_tubes(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=
     _tables.append((host, dev, ev))
     stream = torch.cuda.current_stream(device)
     for group in keep_alive:  # contiguous() may have made copies: the allocator must not hand them out before the launch has run
+        for t in group:
+            if t is not None:
+                t.record_stream(stream)
+    return results[0] if single else results
+
+
+# ---- grounded tubes redacted in decoded frames (td_tube_redact, csrc/redact.hip) ---------------------------------------------
+MAX_RECTS = 8
+REDACT_MODES = ("fill", "mosaic", "blur")
+
+
+def _redact_what(mode, cell, radius, margin, invert):
+    if mode not in REDACT_MODES:
+        raise ValueError(f"mode {mode!r}: one of {REDACT_MODES}")
+    try:
+        num, den = margin
+    except (TypeError, ValueError):
+        raise ValueError(f"margin {margin!r}: two integers") from None
+    if any(isinstance(v, bool) or int(v) != v for v in (cell, radius, num, den)):
+        raise ValueError(f"cell {cell!r}, radius {radius!r} and margin {margin!r}: integers")
+    cell, radius, num, den = int(cell), int(radius), int(num), int(den)
+    if mode == "mosaic" and not (2 <= cell <= 256 and cell % 2 == 0):
+        raise ValueError(f"cell {cell}: an even number in 2..256")
+    if mode == "blur" and not 1 <= radius <= 64:
+        raise ValueError(f"radius {radius}: 1..64")
+    if not 1 <= den <= MAX_MARGIN_DEN:
+        raise ValueError(f"margin denominator {den}: 1..{MAX_MARGIN_DEN}")
+    if not 0 <= num <= 4 * den:
+        raise ValueError(f"margin {num}/{den}: between 0 and 4")
+    if invert not in (0, 1, False, True):
+        raise ValueError(f"invert {invert!r}: a bool")
+    return REDACT_MODES.index(mode), cell, radius, num, den, int(bool(invert))
+
+
+def redact_job(src: int, T: int, sh: int, sw: int, boxes: int, n_tube: int, K: int = 1, dst: Optional[int] = None, pix_fmt: str = "rgb24", span: Optional[int] = None,
+               frame_map: Optional[int] = None, mode: str = "mosaic", cell: int = 16, radius: int = 8, color=(0, 0, 0), margin: Tuple[int, int] = (0, 1), invert: bool = False,
+               src_planes: Optional[Sequence[int]] = None, src_pitches: Optional[Sequence[int]] = None, src_frame_stride: Optional[int] = None,
+               dst_planes: Optional[Sequence[int]] = None, dst_pitches: Optional[Sequence[int]] = None, dst_frame_stride: Optional[int] = None):
+    """One ``td_redact_job``: T frames of sh x sw in ``pix_fmt`` at device address ``src``, redacted into ``dst`` (None: in
+    place).  ``boxes`` (fp32 [n_tube][K][4], required), ``span`` (int64 [K][2]) and ``frame_map`` (int32 [T]) are device
+    addresses or None; ``color`` is three bytes in the FRAMES' colour space (``color_in_space``).  Without ``*_planes`` /
+    ``*_pitches`` / ``*_frame_stride`` the frames are tightly packed (``DeviceFrames``); else the planes are the device
+    addresses of frame 0's planes and the pitches their row pitches."""
+    from . import _hip
+
+    T, sh, sw, n_tube, K = int(T), int(sh), int(sw), int(n_tube), int(K)
+    _check_geometry(pix_fmt, T, sh, sw)
+    if n_tube < 1:
+        raise ValueError(f"n_tube = {n_tube}: at least one tube row")
+    if not 1 <= K <= MAX_RECTS:
+        raise ValueError(f"K = {K}: 1..{MAX_RECTS} rectangles per tube row")
+    if not boxes:
+        raise ValueError("boxes is a device address, not None")
+    code, cell, radius, num, den, inv = _redact_what(mode, cell, radius, margin, invert)
+    fmt, tight, sizes = _planes(pix_fmt, sh, sw)
+    j = _hip.RedactJob()
+    (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride = _describe(src, sizes, tight, src_planes, src_pitches, src_frame_stride)
+    if dst is None and dst_planes is None:
+        (j.dst0, j.dst1, j.dst2), (j.dst_pitch0, j.dst_pitch1, j.dst_pitch2), j.dst_frame_stride = (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride
+    else:
+        (j.dst0, j.dst1, j.dst2), (j.dst_pitch0, j.dst_pitch1, j.dst_pitch2), j.dst_frame_stride = _describe(dst, sizes, tight, dst_planes, dst_pitches, dst_frame_stride)
+    j.fmt, j.T, j.sh, j.sw = fmt, T, sh, sw
+    j.boxes, j.span, j.frame_map = boxes, span, frame_map
+    j.n_tube, j.K, j.mode, j.invert = n_tube, K, code, inv
+    j.margin_num, j.margin_den, j.cell, j.radius = num, den, cell, radius
+    j.color[:] = _rgb3("color", color)
+    return j
+
+
+def tube_redact(jobs: Sequence, device) -> tuple:
+    """One td_tube_redact launch on the current stream with freshly allocated job tables; returns them: the caller keeps
+    them alive until the stream has passed the launch (``redact`` recycles its own instead)."""
+    from . import _hip
+
+    lib = _hip.lib()
+    nb = int(lib.td_tube_redact_table_bytes(len(jobs)))
+    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
+    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
+    arr = (_hip.RedactJob * len(jobs))(*jobs)
+    _hip.check(lib.td_tube_redact(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_tube_redact")
+    return host, dev
+
+
+def redact(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=None, frame_map=None, mode: str = "mosaic", cell: int = 16, radius: int = 8,
+           color=(0, 0, 0), margin: Tuple[int, int] = (0, 1), invert: bool = False, out: Union[None, DeviceFrames, Sequence[DeviceFrames]] = None):
+    """Hide grounded tubes in decoded frames - or, with ``invert``, everything but them: ONE launch for one clip or for a list
+    of clips (then ``boxes``, ``span``, ``frame_map`` and ``out`` are lists too, or None).  Per clip:
+      boxes      fp32 (n_tube, 4) or (n_tube, K, 4) xyxy in the frames' pixels on the device: one tube, or the K <= 8 tubes of a
+                 clip whose UNION is hidden in one pass;
+      span       int64 (2,) or (K, 2): a row of ``sted_decode``'s output or a pick of ``moments_topk`` per tube; None: all rows;
+      frame_map  int32 (T,): the tube row of each frame; None: frame t is row t;
+      out        ``DeviceFrames`` of the same geometry to write into; the clip itself: in place (not for "blur"); None: a new buffer.
+    ``mode``: "fill" (``color``, RGB, converted by ``color_in_space``), "mosaic" (``cell`` even, 2..256) or "blur" (a box mean of
+    ``radius`` 1..64); ``margin`` = (num, den) grows every box by num / den of its side first.  The rule is exact and stated in
+    include/tubedetr_hip.h.  Returns the redacted ``DeviceFrames`` (a list for a list).  Nothing here synchronises or copies to
+    the host."""
+    from . import _hip
+
+    single = isinstance(frames, DeviceFrames)
+    clips = [frames] if single else list(frames)
+    n = len(clips)
+    if n == 0:
+        return []
+    if not isinstance(clips[0], DeviceFrames):
+        raise ValueError("frames: DeviceFrames on one device")
+    device = clips[0].data.device
+    _redact_what(mode, cell, radius, margin, invert)
+    color = _rgb3("color", color)
+    boxes_l, span_l, map_l, out_l = (_as_list(v, n, k) for v, k in ((boxes, "boxes"), (span, "span"), (frame_map, "frame_map"), (out, "out")))
+    prepared = []
+    for c, b, s, m, o in zip(clips, boxes_l, span_l, map_l, out_l):  # every refusal comes before the first allocation and the launch
+        if not isinstance(c, DeviceFrames) or c.data.device != device:
+            raise ValueError("frames: DeviceFrames on one device")
+        if b is None:
+            raise ValueError("boxes: a torch.float32 tensor (n_tube, 4) or (n_tube, K, 4) per clip")
+        b = _dev_tensor(b, torch.float32, (4,), "boxes", device)
+        s = _dev_tensor(s, torch.int64, (2,), "span", device)
+        m = _dev_tensor(m, torch.int32, (c.T,), "frame_map", device)
+        if b.dim() not in (2, 3) or b.shape[0] < 1 or m is not None and m.dim() != 1:
+            raise ValueError("boxes (n_tube, 4) or (n_tube, K, 4) with n_tube >= 1, frame_map (T,)")
+        K = 1 if b.dim() == 2 else int(b.shape[1])
+        if not 1 <= K <= MAX_RECTS:
+            raise ValueError(f"boxes carry K = {K} rectangles per tube row: 1..{MAX_RECTS}")
+        if s is not None and not (s.dim() == 1 and K == 1 or s.dim() == 2 and s.shape[0] == K):
+            raise ValueError(f"span: (2,) for one tube, ({K}, 2) for {K}")
+        if o is not None and (not isinstance(o, DeviceFrames) or (o.T, o.h, o.w, o.pix_fmt) != (c.T, c.h, c.w, c.pix_fmt) or o.data.device != device):
+            raise ValueError("out: DeviceFrames of the clip's geometry and pixel format on its device")
+        if o is not None and mode == "blur" and o.data.data_ptr() == c.data.data_ptr():
+            raise ValueError('mode "blur" cannot run in place (out is the clip itself): it reads neighbours that are already rewritten')
+        prepared.append((c, b, s, m, o, K))
+    jobs, keep, results = [], [], []
+    for c, b, s, m, o, K in prepared:
+        if o is None:
+            o = c.empty_like()
+        jobs.append(redact_job(c.data.data_ptr(), c.T, c.h, c.w, b.data_ptr(), b.shape[0], K, o.data.data_ptr(), c.pix_fmt, _hip.ptr(s), _hip.ptr(m), mode, cell, radius,
+                               color_in_space(color, c.pix_fmt, c.matrix, c.full_range), margin, invert))
+        keep.append((c.data, b, s, m))
+        results.append(o)
+    lib = _hip.lib()
+    nb = int(lib.td_tube_redact_table_bytes(n))
+    host, dev, ev = _take_table(nb, device)
+    arr = (_hip.RedactJob * n)(*jobs)
+    _hip.check(lib.td_tube_redact(arr, n, host.data_ptr(), dev.data_ptr(), host.numel(), _hip.stream_ptr()), "td_tube_redact")
+    ev.record()
+    _tables.append((host, dev, ev))
+    stream = torch.cuda.current_stream(device)
+    for group in keep:  # contiguous() may have made copies: the allocator must not hand them out before the launch has run
         for t in group:
             if t is not None:
                 t.record_stream(stream)
