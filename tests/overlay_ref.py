@@ -5,6 +5,8 @@ Frames are "planes" as tests/test_yuv_input_gpu.py makes them: rgb24 one array (
 U (T, ch, cw), V (T, ch, cw)); nv12 (Y, UV (T, ch, cw, 2)); ch = (h + 1) // 2, cw = (w + 1) // 2."""
 import numpy as np
 
+from tube_rule_ref import rounded_corners as box_corners  # fp32 xyxy -> (x0, y0, x1, y1) ints, or None for a box that draws nothing
+
 
 def blend(v, c, a):
     """(v (256 - a) + c a + 128) >> 8 on int64 arrays."""
@@ -27,18 +29,6 @@ def heat_alpha_map(q, sh, sw, heat_alpha):
     q00, q01, q10, q11 = q[iy][:, ix], q[iy][:, ix1], q[iy1][:, ix], q[iy1][:, ix1]
     h = ((256 - fy) * ((256 - fx) * q00 + fx * q01) + fy * ((256 - fx) * q10 + fx * q11) + 32768) >> 16
     return (h * heat_alpha + 127) // 255
-
-
-def box_corners(box):
-    """fp32 xyxy -> (x0, y0, x1, y1) ints, or None for a box that draws nothing."""
-    b = np.asarray(box, dtype=np.float32)
-    if not np.isfinite(b).all():
-        return None
-    b = np.clip(b, np.float32(-(2 ** 20)), np.float32(2 ** 20))
-    x0, y0, x1, y1 = (int(np.floor(v + np.float32(0.5))) for v in b)
-    if x1 <= x0 or y1 <= y0:
-        return None
-    return x0, y0, x1, y1
 
 
 def box_alpha_map(box, sh, sw, th):

@@ -3,30 +3,17 @@ numbers in the comments are the rule's steps.  Planes come and go in the layout 
 rgb24 (T, sh, sw, 3); yuv420p (Y, U, V); nv12 (Y, UV) with UV (T, ch, cw, 2)."""
 import numpy as np
 
+from tube_rule_ref import box_in_frame, round_coord  # noqa: F401 (3: round_coord; 2 - 5: box_in_frame)
+
 MODES = ("fill", "mosaic", "blur")
-
-
-def round_coord(v):
-    """3: fp32, finite values clamped to +-2^20, floor(v + 0.5)."""
-    v = np.float32(v)
-    v = np.float32(min(max(v, np.float32(-1048576.0)), np.float32(1048576.0)))
-    return int(np.floor(np.float32(v + np.float32(0.5))))
 
 
 def snapped_rect(box, sh, sw, mode, cell, margin):
     """Steps 2 (finiteness) to 6 for one box: (X0, X1, Y0, Y1) in luma pixels, or None when the rectangle is absent."""
-    box = np.asarray(box, dtype=np.float32)
-    if not np.isfinite(box).all():
+    w = box_in_frame(box, sh, sw, margin)
+    if w is None:
         return None
-    x0, y0, x1, y1 = (round_coord(v) for v in box)
-    if x1 <= x0 or y1 <= y0:
-        return None
-    num, den = margin
-    mx, my = ((x1 - x0) * num) // den, ((y1 - y0) * num) // den  # 4 (non-negative operands)
-    x0, x1, y0, y1 = x0 - mx, x1 + mx, y0 - my, y1 + my
-    wx0, wx1, wy0, wy1 = max(x0, 0), min(x1, sw), max(y0, 0), min(y1, sh)  # 5
-    if wx1 <= wx0 or wy1 <= wy0:
-        return None
+    wx0, wx1, wy0, wy1 = w
     if mode == "mosaic":  # 6
         return ((wx0 // cell) * cell, min(((wx1 + cell - 1) // cell) * cell, sw), (wy0 // cell) * cell, min(((wy1 + cell - 1) // cell) * cell, sh))
     return (wx0 & ~1, min(wx1 + (wx1 & 1), sw), wy0 & ~1, min(wy1 + (wy1 & 1), sh))

@@ -4,14 +4,9 @@ margin, clamp, output size, valid and the window record) and the composer of the
 Written from the header's text, with Python integers (unbounded) and np.float32 for the rounding step."""
 import numpy as np
 
+from tube_rule_ref import box_in_frame, round_coord  # noqa: F401 (round_coord: tests import it from here)
+
 EMPTY = (0, 0, 0, 0, 0, 0)
-
-
-def round_coord(v) -> int:
-    """(int)floorf(clamp(v, +-2^20) + 0.5f) in fp32."""
-    v = np.float32(v)
-    v = np.minimum(np.maximum(v, np.float32(-1048576.0)), np.float32(1048576.0))
-    return int(np.floor(np.float32(v + np.float32(0.5))))
 
 
 def out_size(ch: int, cw: int, oh: int, ow: int, keep_aspect) -> tuple:
@@ -25,19 +20,11 @@ def out_size(ch: int, cw: int, oh: int, ow: int, keep_aspect) -> tuple:
 
 def box_window(box, sh: int, sw: int, oh: int, ow: int, margin=(0, 1), keep_aspect=True) -> tuple:
     """(wy0, wx0, ch, cw, rh, rw) of one box in an sh x sw frame, or EMPTY (steps 2 - 6 without the span and the tube row)."""
-    b = np.asarray(box, dtype=np.float32)
-    if not np.isfinite(b).all():
+    w = box_in_frame(box, sh, sw, margin)  # steps 2 (finiteness) to 5
+    if w is None:
         return EMPTY
-    x0, y0, x1, y1 = (round_coord(v) for v in b)
-    if x1 <= x0 or y1 <= y0:
-        return EMPTY
-    num, den = int(margin[0]), int(margin[1])
-    mx, my = ((x1 - x0) * num) // den, ((y1 - y0) * num) // den
-    x0, x1, y0, y1 = x0 - mx, x1 + mx, y0 - my, y1 + my
-    wx0, wx1, wy0, wy1 = max(x0, 0), min(x1, sw), max(y0, 0), min(y1, sh)
+    wx0, wx1, wy0, wy1 = w
     cw, ch = wx1 - wx0, wy1 - wy0
-    if cw <= 0 or ch <= 0:
-        return EMPTY
     rh, rw = out_size(ch, cw, oh, ow, keep_aspect)
     return wy0, wx0, ch, cw, rh, rw
 

@@ -49,7 +49,7 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
     _check_compiler(hipcc)
-    headers = [os.path.join(CSRC, "td_common.h"), os.path.join(CSRC, "resample_dev.h"), os.path.join(CSRC, "gemm_route.h"),os.path.join(os.path.dirname(HERE), "include", "tubedetr_hip.h")]
+    headers = [os.path.join(CSRC, "td_common.h"), os.path.join(CSRC, "resample_dev.h"), os.path.join(CSRC, "frame_jobs.h"), os.path.join(CSRC, "gemm_route.h"),os.path.join(os.path.dirname(HERE), "include", "tubedetr_hip.h")]
     objs, jobs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

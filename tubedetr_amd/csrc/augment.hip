@@ -21,7 +21,8 @@
 // converted frame, and the tables and the producing half are shared: bit equality with the rgb24 path by construction.
 // Every plane has its own extent guard.  The 3 dword stores of a lane go to dwords 3d, 3d + 1, 3d + 2: a stride of 3
 // dwords over the lanes, coprime with the 32 banks of a store, so each of the three is conflict-free.
-// tap(), the yuv staging and the blend live in resample_dev.h: td_tube_crop (tube_crop.hip) is defined by this kernel's bytes and shares them.
+// tap(), the yuv staging and the blend live in resample_dev.h: td_tube_crop (tube_crop.hip) is defined by this kernel's bytes and shares them;
+// the job search, the plane geometry and the table upload + launch are every job-table kernel's: frame_jobs.h.
 #include <algorithm>
 #include <type_traits>
 
@@ -59,12 +60,7 @@ template <typename P>
 __global__ __launch_bounds__(kThreads) void clip_resample_kernel(const P* __restrict__ tab, int n_jobs) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, b = blockIdx.x;
-  int lo = 0, hi = n_jobs - 1;
-  while (lo < hi) {  // last job whose first block is <= b (uniform: scalar loads)
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].block_begin <= b) lo = mid; else hi = mid - 1;
-  }
-  const P p = tab[lo];
+  const P p = tab[find_job(tab, n_jobs, b)];
   const int local = b - p.block_begin;
   const int band = local % p.nbands, chunk = local / p.nbands;
   const int yb = band * p.R;
@@ -191,23 +187,14 @@ __global__ __launch_bounds__(kThreads) void clip_resample_kernel(const P* __rest
   }
 }
 
-template <typename P>
-static size_t table_bytes(int n_jobs) { return (((size_t)n_jobs * sizeof(P)) + 255) & ~(size_t)255; }
-
 static void set_format(ResampleParams&, const td_resample_src_job&, int) {}
 static void set_format(SrcParams& p, const td_resample_src_job& j, int ncols) {
   p.fmt = j.fmt;
   if (j.fmt == TD_SRC_RGB24) return;
-  const long long cw = (j.sw + 1) / 2, ch = (j.sh + 1) / 2, last = (long long)(j.T - 1) * j.frame_stride;
-  p.src_bytes = last + (long long)(j.sh - 1) * j.pitch0 + j.sw;
-  p.plane1 = (const unsigned char*)j.plane1; p.pitch1 = j.pitch1;
-  if (j.fmt == TD_SRC_NV12) {
-    p.bytes1 = last + (ch - 1) * j.pitch1 + 2 * cw;
-  } else {
-    p.bytes1 = last + (ch - 1) * j.pitch1 + cw;
-    p.plane2 = (const unsigned char*)j.plane2; p.pitch2 = j.pitch2;
-    p.bytes2 = last + (ch - 1) * j.pitch2 + cw;
-  }
+  const PlaneGeom g = plane_geom(j.fmt, j.sh, j.sw);
+  p.src_bytes = plane_extent(g, 0, j.pitch0, j.frame_stride, j.T);
+  p.plane1 = (const unsigned char*)j.plane1; p.pitch1 = j.pitch1; p.bytes1 = plane_extent(g, 1, j.pitch1, j.frame_stride, j.T);
+  if (j.fmt == TD_SRC_I420) { p.plane2 = (const unsigned char*)j.plane2; p.pitch2 = j.pitch2; p.bytes2 = plane_extent(g, 2, j.pitch2, j.frame_stride, j.T); }
   p.nd = (ncols + 3 + 3) >> 2;  // + 3: the Y row is staged from its address rounded down to a dword
   p.slot_bytes = (12 * p.nd + 15) & ~15;
   const int* k = kYuvCoef[j.matrix][j.full_range];
@@ -253,16 +240,13 @@ static int enqueue(const char* who, bool legacy, const J* jobs, int n_jobs, void
       TD_REQUIRE(j.pitch0 >= 3 * j.sw && j.frame_stride >= (long long)j.pitch0 * (j.sh - 1) + 3 * j.sw,
                  "%s: job %d: row pitch %d / frame stride %lld too small for %d x %d rgb24", who, i, j.pitch0, j.frame_stride, j.sh, j.sw);
     } else {
-      // row bytes and rows of each plane
-      const int cw = (j.sw + 1) / 2, ch = (j.sh + 1) / 2;
-      const int n_planes = j.fmt == TD_SRC_RGB24 ? 1 : j.fmt == TD_SRC_NV12 ? 2 : 3;
-      const int row_bytes[3] = {j.fmt == TD_SRC_RGB24 ? 3 * j.sw : j.sw, j.fmt == TD_SRC_NV12 ? 2 * cw : cw, cw};
-      const int rows[3] = {j.sh, ch, ch}, pitch[3] = {j.pitch0, j.pitch1, j.pitch2};
-      for (int k = 0; k < n_planes; k++)
-        TD_REQUIRE(pitch[k] >= row_bytes[k], "%s: job %d: pitch %d of plane %d is below its row of %d bytes", who, i, pitch[k], k, row_bytes[k]);
-      for (int k = 0; k < n_planes; k++)
-        TD_REQUIRE(j.frame_stride >= (long long)pitch[k] * (rows[k] - 1) + row_bytes[k],
-                   "%s: job %d: frame stride %lld is smaller than plane %d needs (%d rows of pitch %d)", who, i, j.frame_stride, k, rows[k], pitch[k]);
+      const PlaneGeom g = plane_geom(j.fmt, j.sh, j.sw);  // this entry point's own wording and order: all pitches, then all strides
+      const int pitch[3] = {j.pitch0, j.pitch1, j.pitch2};
+      for (int k = 0; k < g.n_planes; k++)
+        TD_REQUIRE(pitch[k] >= g.row_bytes[k], "%s: job %d: pitch %d of plane %d is below its row of %d bytes", who, i, pitch[k], k, g.row_bytes[k]);
+      for (int k = 0; k < g.n_planes; k++)
+        TD_REQUIRE(j.frame_stride >= plane_extent(g, k, pitch[k]),
+                   "%s: job %d: frame stride %lld is smaller than plane %d needs (%d rows of pitch %d)", who, i, j.frame_stride, k, g.rows[k], pitch[k]);
     }
     TD_REQUIRE(j.flip == 0 || j.flip == 1, "%s: job %d: flip must be 0 or 1", who, i);
     if (j.planar)
@@ -291,39 +275,26 @@ static int enqueue(const char* who, bool legacy, const J* jobs, int n_jobs, void
     TD_REQUIRE(need <= kMaxLds, "%s: job %d needs %zu bytes of LDS (destination row of %d pixels, %d source columns)", who, i, need, p.W, ncols);
     lds = std::max(lds, need);
     p.nbands = cdiv(p.H, p.R);
-    p.block_begin = (int)blocks;
-    blocks += (long long)p.nbands * cdiv(p.T, kFrameChunk);
-    TD_REQUIRE(blocks < (1LL << 31), "%s: too many workgroups", who);
+    if (int rc = add_blocks(who, blocks, (long long)p.nbands * cdiv(p.T, kFrameChunk), p.block_begin)) return rc;
     host[n++] = p;
   }
-  if (n == 0) return TD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(table_dev, host, (size_t)n * sizeof(P), hipMemcpyHostToDevice, st) != hipSuccess) {
-    set_error("%s: job table upload failed", who);
-    return TD_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(clip_resample_kernel<P>, dim3((unsigned)blocks), dim3(kThreads), lds, st, (const P*)table_dev, n);
-  return check_launch(who);
+  return upload_and_launch(clip_resample_kernel<P>, blocks, lds, host, table_dev, n, stream, who);
 }
 
 }  // namespace td
 
 using namespace td;
 
-extern "C" size_t td_clip_resample_table_bytes(int n_jobs) { return n_jobs > 0 ? table_bytes<ResampleParams>(n_jobs) : 0; }
+extern "C" size_t td_clip_resample_table_bytes(int n_jobs) { return table_bytes<ResampleParams>(n_jobs); }
 
 extern "C" int td_clip_resample(const td_resample_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes_, td_stream_t stream) {
-  TD_REQUIRE(jobs && n_jobs > 0 && n_jobs <= 65536, "td_clip_resample: no jobs (or more than 65536)");
-  TD_REQUIRE(table_host && table_dev && table_bytes_ >= td_clip_resample_table_bytes(n_jobs),
-             "td_clip_resample: job-table workspace missing or smaller than td_clip_resample_table_bytes(%d)", n_jobs);
+  if (int rc = check_workspace<ResampleParams>("td_clip_resample", jobs, n_jobs, table_host, table_dev, table_bytes_)) return rc;
   return enqueue<ResampleParams>("td_clip_resample", true, jobs, n_jobs, table_host, table_dev, stream);
 }
 
-extern "C" size_t td_clip_resample_src_table_bytes(int n_jobs) { return n_jobs > 0 ? table_bytes<SrcParams>(n_jobs) : 0; }
+extern "C" size_t td_clip_resample_src_table_bytes(int n_jobs) { return table_bytes<SrcParams>(n_jobs); }
 
 extern "C" int td_clip_resample_src(const td_resample_src_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes_, td_stream_t stream) {
-  TD_REQUIRE(jobs && n_jobs > 0 && n_jobs <= 65536, "td_clip_resample_src: no jobs (or more than 65536)");
-  TD_REQUIRE(table_host && table_dev && table_bytes_ >= td_clip_resample_src_table_bytes(n_jobs),
-             "td_clip_resample_src: job-table workspace missing or smaller than td_clip_resample_src_table_bytes(%d)", n_jobs);
+  if (int rc = check_workspace<SrcParams>("td_clip_resample_src", jobs, n_jobs, table_host, table_dev, table_bytes_)) return rc;
   return enqueue<SrcParams>("td_clip_resample_src", false, jobs, n_jobs, table_host, table_dev, stream);
 }

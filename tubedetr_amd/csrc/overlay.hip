@@ -11,38 +11,26 @@
 //     same integer as the header's form, below 2^24), so a luma byte costs one table dword, two 16-bit LDS reads and two multiplies;
 //   * a lane owns an ALIGNED run of 16 bytes of a destination row (the rows of the tile are spread over the whole workgroup):
 //     one 16-byte load when the source row has the same alignment (in place, equal pitches), 4 dwords when it agrees modulo 4,
-//     bytes else; one 16-byte store.  Only the first / last run of a tile's row, which it shares with the row padding or
-//     with the neighbour tile, is loaded and stored by bytes - so the in-place case has no hazard: no lane reads or writes
-//     a byte that another lane writes;
+//     bytes else; one 16-byte store (load_run / store_run in frame_jobs.h, which is also why the in-place case has no hazard);
 //   * the outline touches few runs: a run whose columns and rows miss it (two interval tests) skips the box layer, and with
 //     no other layer on the frame its 16 bytes go from the load to the store untouched;
 //   * the U and V rows of an I420 frame are walked together when their destination rows agree modulo 16 (the host checks:
 //     any tightly packed frame whose chroma plane is a multiple of 16 bytes), and the two bytes of an NV12 pair share one
 //     evaluation: a block's alphas are computed once for both components;
 //   * the blend (v (256 - a) + c a + 128) >> 8 cannot leave [0, 255], so there is no clamp here and nothing for the
-//     compiler to fuse into a packed shift-and-clamp (see shift_clamp_u8 in augment.hip before adding one).
+//     compiler to fuse into a packed shift-and-clamp (see shift_clamp_u8 in resample_dev.h before adding one).
 // The table's pointers are loaded from memory: they are declared global so that loads and stores are global_*, not flat_*
-// (which would also take the LDS path the tables need).
-#include <algorithm>
-#include <cmath>
-
-#include "td_common.h"
+// (which would also take the LDS path the tables need).  The job search, the byte runs, the steps of the box rule and the host's
+// plane checks and launch are the family's: frame_jobs.h.
+#include "frame_jobs.h"
 
 namespace td {
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kTileRows = 16;      // luma rows per workgroup (even)
 constexpr int kMaxTileCols = 2048; // luma columns per workgroup (the column table's size)
-constexpr int kMaxSide = 16384;    // (2 y + 1) * 256 * 128 stays below 2^30
 constexpr int kMaxMap = 256;
-constexpr int kRun = 16;           // bytes of a row per lane
-
-#define TD_GLOBAL __attribute__((address_space(1)))
-typedef const TD_GLOBAL unsigned char* gcbyte_ptr;
-typedef TD_GLOBAL unsigned char* gbyte_ptr;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct OverlayParams {
   const unsigned char* src[3];
@@ -78,8 +66,6 @@ __device__ __forceinline__ uint32_t blend(uint32_t v, uint32_t c, uint32_t a) { 
 // g = clamp(((2 v + 1) m 128) / n - 128, 0, 256 (m - 1))
 __device__ __forceinline__ int map_coord(int v, int m, int n) { return min(max(((2 * v + 1) * m * 128) / n - 128, 0), 256 * (m - 1)); }
 
-__device__ __forceinline__ int round_coord(float v) { return (int)floorf(fminf(fmaxf(v, -1048576.f), 1048576.f) + 0.5f); }
-
 struct Frame {  // what is uniform over a tile
   uint32_t a_dim;
   int heat_on, box_on, heat_alpha, mw;
@@ -112,38 +98,6 @@ __device__ __forceinline__ uint32_t layers(const Frame& f, bool boxed, uint32_t 
   return v;
 }
 
-// bytes [o0, o0 + 16) of a row, of which [v0, v1) belong to the tile: no other byte is touched
-__device__ __forceinline__ void load_run(const unsigned char* rowp, int o0, int v0, int v1, uint32_t in[4]) {
-  const unsigned char* a = rowp + o0;
-  const bool full = v0 == o0 && v1 == o0 + kRun;
-  if (full && ((uintptr_t)a & 15) == 0) {
-    const u32x4 v = *(const TD_GLOBAL u32x4*)a;
-    in[0] = v.x; in[1] = v.y; in[2] = v.z; in[3] = v.w;
-  } else if (full && ((uintptr_t)a & 3) == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) in[k] = ((const TD_GLOBAL uint32_t*)a)[k];
-  } else {
-    in[0] = in[1] = in[2] = in[3] = 0;
-#pragma unroll
-    for (int j = 0; j < kRun; j++)
-      if (o0 + j >= v0 && o0 + j < v1) in[j >> 2] |= (uint32_t)((gcbyte_ptr)a)[j] << (8 * (j & 3));
-  }
-}
-
-// rowp + o0 is 16-byte aligned
-__device__ __forceinline__ void store_run(unsigned char* rowp, int o0, int v0, int v1, const uint32_t out[4]) {
-  unsigned char* a = rowp + o0;
-  if (v0 == o0 && v1 == o0 + kRun) {
-    u32x4 v;
-    v.x = out[0]; v.y = out[1]; v.z = out[2]; v.w = out[3];
-    *(TD_GLOBAL u32x4*)a = v;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kRun; j++)
-      if (o0 + j >= v0 && o0 + j < v1) ((gbyte_ptr)a)[j] = (unsigned char)(out[j >> 2] >> (8 * (j & 3)));
-  }
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kThreads) void tube_overlay_kernel(const OverlayParams* __restrict__ tab, int n_jobs) {
@@ -151,12 +105,7 @@ __global__ __launch_bounds__(kThreads) void tube_overlay_kernel(const OverlayPar
   __shared__ uint32_t row[kTileRows];
   __shared__ unsigned short vb[kTileRows * kMaxMap];
   const int tid = threadIdx.x, b = blockIdx.x;
-  int lo = 0, hi = n_jobs - 1;
-  while (lo < hi) {  // last job whose first block is <= b (uniform: scalar loads)
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].block_begin <= b) lo = mid; else hi = mid - 1;
-  }
-  const OverlayParams p = tab[lo];
+  const OverlayParams p = tab[find_job(tab, n_jobs, b)];
   int local = b - p.block_begin;
   const int tx = local % p.ntx; local /= p.ntx;
   const int ty = local % p.nty;
@@ -165,10 +114,9 @@ __global__ __launch_bounds__(kThreads) void tube_overlay_kernel(const OverlayPar
   const int yb = ty * kTileRows, ye = min(yb + kTileRows, p.sh);
 
   // ---- what the frame asks for (uniform)
-  const int r = p.frame_map ? ((const TD_GLOBAL int*)p.frame_map)[t] : t;
+  const int r = tube_row(p.frame_map, t);
   const bool live = r >= 0 && r < p.n_tube;
-  bool in_span = true;
-  if (p.span) { const long long s0 = ((const TD_GLOBAL long long*)p.span)[0], s1 = ((const TD_GLOBAL long long*)p.span)[1]; in_span = r >= s0 && r <= s1; }
+  const bool in_span = row_in_span(p.span, 0, r);
   Frame f;
   f.a_dim = (live && p.span && !in_span) ? (uint32_t)p.dim_alpha : 0u;
   f.heat_on = live && p.heat != nullptr;
@@ -176,15 +124,7 @@ __global__ __launch_bounds__(kThreads) void tube_overlay_kernel(const OverlayPar
   f.box_c = p.box_c; f.heat_c = p.heat_c; f.dim_c = p.dim_c;
   f.x0 = f.x1 = 0;
   int y0 = 0, y1 = 0;
-  f.box_on = 0;
-  if (live && p.boxes && in_span) {
-    const TD_GLOBAL float* bx = (const TD_GLOBAL float*)p.boxes + 4 * (long long)r;
-    const float c0 = bx[0], c1 = bx[1], c2 = bx[2], c3 = bx[3];
-    if (isfinite(c0) && isfinite(c1) && isfinite(c2) && isfinite(c3)) {
-      f.x0 = round_coord(c0); y0 = round_coord(c1); f.x1 = round_coord(c2); y1 = round_coord(c3);
-      f.box_on = f.x1 > f.x0 && y1 > y0;
-    }
-  }
+  f.box_on = live && p.boxes && in_span && rounded_box(p.boxes, r, f.x0, y0, f.x1, y1);
 
   // ---- the tile's tables
   if (f.heat_on || f.box_on) {
@@ -308,10 +248,6 @@ __global__ __launch_bounds__(kThreads) void tube_overlay_kernel(const OverlayPar
 
 namespace {
 
-struct Plane { const unsigned char* p; long long bytes; };
-
-size_t overlay_table_bytes(int n_jobs) { return (((size_t)n_jobs * sizeof(OverlayParams)) + 255) & ~(size_t)255; }
-
 uint32_t pack3(const unsigned char c[3]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16); }
 
 }  // namespace
@@ -320,13 +256,11 @@ uint32_t pack3(const unsigned char c[3]) { return (uint32_t)c[0] | ((uint32_t)c[
 
 using namespace td;
 
-extern "C" size_t td_tube_overlay_table_bytes(int n_jobs) { return n_jobs > 0 ? overlay_table_bytes(n_jobs) : 0; }
+extern "C" size_t td_tube_overlay_table_bytes(int n_jobs) { return table_bytes<OverlayParams>(n_jobs); }
 
 extern "C" int td_tube_overlay(const td_overlay_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream) {
   const char* who = "td_tube_overlay";
-  TD_REQUIRE(jobs && n_jobs > 0 && n_jobs <= 65536, "%s: no jobs (or more than 65536)", who);
-  TD_REQUIRE(table_host && table_dev && table_bytes >= td_tube_overlay_table_bytes(n_jobs),
-             "%s: job-table workspace missing or smaller than td_tube_overlay_table_bytes(%d)", who, n_jobs);
+  if (int rc = check_workspace<OverlayParams>(who, jobs, n_jobs, table_host, table_dev, table_bytes)) return rc;
   OverlayParams* host = (OverlayParams*)table_host;
   int n = 0;
   long long blocks = 0;
@@ -340,40 +274,18 @@ extern "C" int td_tube_overlay(const td_overlay_job* jobs, int n_jobs, void* tab
     TD_REQUIRE(j.heat_alpha >= 0 && j.heat_alpha <= 256, "%s: job %d: heat_alpha %d outside [0, 256]", who, i, j.heat_alpha);
     TD_REQUIRE(j.dim_alpha >= 0 && j.dim_alpha <= 256, "%s: job %d: dim_alpha %d outside [0, 256]", who, i, j.dim_alpha);
     TD_REQUIRE(!j.heat || (j.mh >= 1 && j.mw >= 1 && j.mh <= kMaxMap && j.mw <= kMaxMap), "%s: job %d: token grid mh x mw = %d x %d outside 1..%d", who, i, j.mh, j.mw, kMaxMap);
-    const int n_planes = j.fmt == TD_SRC_RGB24 ? 1 : j.fmt == TD_SRC_NV12 ? 2 : 3;
-    const int cw = (j.sw + 1) / 2, ch = (j.sh + 1) / 2;
-    const int row_bytes[3] = {j.fmt == TD_SRC_RGB24 ? 3 * j.sw : j.sw, j.fmt == TD_SRC_NV12 ? 2 * cw : cw, cw};
-    const int rows[3] = {j.sh, ch, ch};
-    const void* sp[3] = {j.src0, j.src1, j.src2};
-    void* dp[3] = {j.dst0, j.dst1, j.dst2};
-    const int spitch[3] = {j.src_pitch0, j.src_pitch1, j.src_pitch2}, dpitch[3] = {j.dst_pitch0, j.dst_pitch1, j.dst_pitch2};
-    for (int k = 0; k < n_planes; k++) {
-      TD_REQUIRE(sp[k], "%s: job %d: src%d is null", who, i, k);
-      TD_REQUIRE(dp[k], "%s: job %d: dst%d is null", who, i, k);
-      TD_REQUIRE(spitch[k] >= row_bytes[k], "%s: job %d: src_pitch%d = %d is below its row of %d bytes", who, i, k, spitch[k], row_bytes[k]);
-      TD_REQUIRE(dpitch[k] >= row_bytes[k], "%s: job %d: dst_pitch%d = %d is below its row of %d bytes", who, i, k, dpitch[k], row_bytes[k]);
-      TD_REQUIRE(j.src_frame_stride >= (long long)spitch[k] * (rows[k] - 1) + row_bytes[k],
-                 "%s: job %d: src_frame_stride %lld is smaller than plane %d needs (%d rows of pitch %d)", who, i, j.src_frame_stride, k, rows[k], spitch[k]);
-      TD_REQUIRE(j.dst_frame_stride >= (long long)dpitch[k] * (rows[k] - 1) + row_bytes[k],
-                 "%s: job %d: dst_frame_stride %lld is smaller than plane %d needs (%d rows of pitch %d)", who, i, j.dst_frame_stride, k, rows[k], dpitch[k]);
-    }
+    const PlaneGeom g = plane_geom(j.fmt, j.sh, j.sw);
+    const PlaneSet sets[2] = {{"src", {j.src0, j.src1, j.src2}, {j.src_pitch0, j.src_pitch1, j.src_pitch2}, j.src_frame_stride},
+                              {"dst", {j.dst0, j.dst1, j.dst2}, {j.dst_pitch0, j.dst_pitch1, j.dst_pitch2}, j.dst_frame_stride}};
+    const PlaneSet &sp = sets[0], &dp = sets[1];
+    if (int rc = check_planes(who, i, g, sets, 2)) return rc;
     if (j.T == 0) continue;
-    // a destination plane is its source plane, or touches no source plane (byte ranges from the first row of frame 0 to the last row of frame T - 1)
-    Plane s[3], d[3];
-    for (int k = 0; k < n_planes; k++) {
-      s[k] = Plane{(const unsigned char*)sp[k], (long long)(j.T - 1) * j.src_frame_stride + (long long)spitch[k] * (rows[k] - 1) + row_bytes[k]};
-      d[k] = Plane{(const unsigned char*)dp[k], (long long)(j.T - 1) * j.dst_frame_stride + (long long)dpitch[k] * (rows[k] - 1) + row_bytes[k]};
-    }
-    for (int k = 0; k < n_planes; k++) {
-      if (dp[k] == sp[k] && dpitch[k] == spitch[k] && j.dst_frame_stride == j.src_frame_stride) continue;  // in place
-      for (int m = 0; m < n_planes; m++)
-        TD_REQUIRE(d[k].p + d[k].bytes <= s[m].p || s[m].p + s[m].bytes <= d[k].p,
-                   "%s: job %d: dst%d overlaps src%d without being the same plane (pointer, pitch and frame stride)", who, i, k, m);
-    }
+    for (int k = 0; k < g.n_planes; k++)
+      if (int rc = check_inplace_or_apart(who, i, g, sp, dp, j.T, k)) return rc;
     OverlayParams p{};
-    for (int k = 0; k < n_planes; k++) {
-      p.src[k] = (const unsigned char*)sp[k]; p.dst[k] = (unsigned char*)dp[k];
-      p.spitch[k] = spitch[k]; p.dpitch[k] = dpitch[k];
+    for (int k = 0; k < g.n_planes; k++) {
+      p.src[k] = (const unsigned char*)sp.p[k]; p.dst[k] = (unsigned char*)dp.p[k];
+      p.spitch[k] = sp.pitch[k]; p.dpitch[k] = dp.pitch[k];
     }
     p.sstride = j.src_frame_stride; p.dstride = j.dst_frame_stride;
     p.fmt = j.fmt; p.T = j.T; p.sh = j.sh; p.sw = j.sw;
@@ -382,22 +294,13 @@ extern "C" int td_tube_overlay(const td_overlay_job* jobs, int n_jobs, void* tab
     p.th = std::min(j.thickness, 1 << 22);  // fills every box the rounding can make; x0 + th stays in int32
     p.box_c = pack3(j.box_color); p.heat_c = pack3(j.heat_color); p.dim_c = pack3(j.dim_color);
     // U and V rows in one walk: every pair of destination rows (row y of frame t of both planes) has the same alignment
-    p.joint = j.fmt == TD_SRC_I420 && (((uintptr_t)dp[1] ^ (uintptr_t)dp[2]) & (kRun - 1)) == 0 && ((dpitch[1] ^ dpitch[2]) & (kRun - 1)) == 0;
+    p.joint = j.fmt == TD_SRC_I420 && (((uintptr_t)dp.p[1] ^ (uintptr_t)dp.p[2]) & (kRun - 1)) == 0 && ((dp.pitch[1] ^ dp.pitch[2]) & (kRun - 1)) == 0;
     p.ntx = cdiv(j.sw, kMaxTileCols);
     p.tile_w = (cdiv(j.sw, p.ntx) + 31) & ~31;  // equal tiles of whole 2 x 2 blocks; their chroma rows split at multiples of 16 bytes
     p.ntx = cdiv(j.sw, p.tile_w);
     p.nty = cdiv(j.sh, kTileRows);
-    p.block_begin = (int)blocks;
-    blocks += (long long)j.T * p.ntx * p.nty;
-    TD_REQUIRE(blocks < (1LL << 31), "%s: too many workgroups", who);
+    if (int rc = add_blocks(who, blocks, (long long)j.T * p.ntx * p.nty, p.block_begin)) return rc;
     host[n++] = p;
   }
-  if (n == 0) return TD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(table_dev, host, (size_t)n * sizeof(OverlayParams), hipMemcpyHostToDevice, st) != hipSuccess) {
-    set_error("%s: job table upload failed", who);
-    return TD_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(tube_overlay_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, (const OverlayParams*)table_dev, n);
-  return check_launch(who);
+  return upload_and_launch(tube_overlay_kernel, blocks, 0, host, table_dev, n, stream, who);
 }

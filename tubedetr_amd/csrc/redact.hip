@@ -11,9 +11,10 @@
 //   * per tile, ONCE: lanes 0..7 evaluate the frame's rectangles (steps 1 - 6 of the rule) into LDS; every lane then builds the
 //     tile's column and row bit tables from them (bit k: inside rectangle k), so a byte's selection is one AND;
 //   * a tile that no rectangle reaches (and invert = 0) is a copy, and IN PLACE its workgroup returns without touching memory;
-//   * the write is overlay.hip's: a lane owns an ALIGNED run of 16 bytes of a destination row, loaded with one 16-byte load
-//     when the source row has the same alignment, 4 dwords when it agrees modulo 4, bytes else; only the first / last run of a
-//     tile's row is handled by bytes, so no lane reads or writes a byte that another workgroup writes.  Two interval tests per
+//   * the write is td_tube_overlay's (load_run / store_run in frame_jobs.h): a lane owns an ALIGNED run of 16 bytes of a
+//     destination row, loaded with one 16-byte load when the source row has the same alignment, 4 dwords when it agrees modulo 4,
+//     bytes else; only the first / last run of a tile's row is handled by bytes, so no lane reads or writes a byte that another
+//     workgroup writes.  Two interval tests per
 //     rectangle that reaches the row say whether a run lies inside one (selected throughout) or outside all (not at all); only a
 //     run that straddles an edge asks the tables byte by byte.  A run without a selected byte goes from the load to the store
 //     untouched; in place it is not touched at all; a FILL run selected throughout is not loaded;
@@ -27,32 +28,21 @@
 //     chains between one set of barriers), so neither direction costs more at a larger radius, except for the halo.  Batches
 //     of the tile that no rectangle reaches skip all of it and are copied.
 // No atomics, no scratch; everything is plain C++ and vector stores.  The table's pointers are loaded from memory: they are
-// declared global so that loads and stores are global_*, not flat_*.
-#include <algorithm>
-#include <cmath>
-
-#include "td_common.h"
+// declared global so that loads and stores are global_*, not flat_*.  Steps 1 - 5 of the rule, the job search, the byte runs and
+// the host's plane checks and launch are the family's: frame_jobs.h.
+#include "frame_jobs.h"
 
 namespace td {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxSide = 16384;
 constexpr int kMaxRects = 8;
-constexpr int kMaxMarginDen = 1024;
-constexpr int kRun = 16;            // bytes of a row per lane
 constexpr int kCols = 256;          // samples per tile row: MOSAIC, BLUR (with the halo)
 constexpr int kFillRows = 64, kFillCols = 1024;
 constexpr int kBlurRows = 64, kBlurBatch = 4;
 constexpr int kMosaicCellRows = 8;  // cell rows per MOSAIC tile, at most
 constexpr int kMaxTileRows = 256;   // one cell row of cell 256
 constexpr int kValBytes = kMosaicCellRows * 128 * 3;  // cp >= 2: at most 128 cells per cell row, 3 channels
-
-#define TD_GLOBAL __attribute__((address_space(1)))
-typedef const TD_GLOBAL unsigned char* gcbyte_ptr;
-typedef TD_GLOBAL unsigned char* gbyte_ptr;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct RedactParams {
   const unsigned char* src[3];
@@ -85,40 +75,6 @@ union ModeTables {
 
 enum { kCopy = 0, kFill = 1, kMosaic = 2, kBlur = 3 };  // where a selected byte's value comes from
 
-__device__ __forceinline__ int round_coord(float v) { return (int)floorf(fminf(fmaxf(v, -1048576.f), 1048576.f) + 0.5f); }
-
-// bytes [o0, o0 + 16) of a row, of which [v0, v1) belong to the tile: no other byte is touched
-__device__ __forceinline__ void load_run(const unsigned char* rowp, int o0, int v0, int v1, uint32_t in[4]) {
-  const unsigned char* a = rowp + o0;
-  const bool full = v0 == o0 && v1 == o0 + kRun;
-  if (full && ((uintptr_t)a & 15) == 0) {
-    const u32x4 v = *(const TD_GLOBAL u32x4*)a;
-    in[0] = v.x; in[1] = v.y; in[2] = v.z; in[3] = v.w;
-  } else if (full && ((uintptr_t)a & 3) == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; k++) in[k] = ((const TD_GLOBAL uint32_t*)a)[k];
-  } else {
-    in[0] = in[1] = in[2] = in[3] = 0;
-#pragma unroll
-    for (int j = 0; j < kRun; j++)
-      if (o0 + j >= v0 && o0 + j < v1) in[j >> 2] |= (uint32_t)((gcbyte_ptr)a)[j] << (8 * (j & 3));
-  }
-}
-
-// rowp + o0 is 16-byte aligned
-__device__ __forceinline__ void store_run(unsigned char* rowp, int o0, int v0, int v1, const uint32_t out[4]) {
-  unsigned char* a = rowp + o0;
-  if (v0 == o0 && v1 == o0 + kRun) {
-    u32x4 v;
-    v.x = out[0]; v.y = out[1]; v.z = out[2]; v.w = out[3];
-    *(TD_GLOBAL u32x4*)a = v;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kRun; j++)
-      if (o0 + j >= v0 && o0 + j < v1) ((gbyte_ptr)a)[j] = (unsigned char)(out[j >> 2] >> (8 * (j & 3)));
-  }
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kThreads) void tube_redact_kernel(const RedactParams* __restrict__ tab, int n_jobs) {
@@ -134,12 +90,7 @@ __global__ __launch_bounds__(kThreads) void tube_redact_kernel(const RedactParam
   auto& pre = tables.blur.pre;
   auto& stage = tables.blur.stage;
   const int tid = threadIdx.x, b = blockIdx.x;
-  int lo = 0, hi = n_jobs - 1;
-  while (lo < hi) {  // last job whose first block is <= b (uniform: scalar loads)
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].block_begin <= b) lo = mid; else hi = mid - 1;
-  }
-  const RedactParams* p = tab + lo;
+  const RedactParams* p = tab + find_job(tab, n_jobs, b);
   int local = b - p->block_begin;
   int pl = 0;
   if (p->n_planes > 1 && local >= p->pbegin[1]) pl = 1;
@@ -160,35 +111,20 @@ __global__ __launch_bounds__(kThreads) void tube_redact_kernel(const RedactParam
   const int yb = ty * th, ye = min(yb + th, rows);
 
   // ---- the frame's rectangles (steps 1 - 6), one per lane
-  const int r = p->frame_map ? ((const TD_GLOBAL int*)p->frame_map)[t] : t;
+  const int r = tube_row(p->frame_map, t);
   if (tid < kMaxRects) {
     int X0 = 0, X1 = 0, Y0 = 0, Y1 = 0;
-    if (tid < p->K && r >= 0 && r < p->n_tube) {
-      bool in_span = true;
-      if (p->span) {
-        const long long s0 = ((const TD_GLOBAL long long*)p->span)[2 * tid], s1 = ((const TD_GLOBAL long long*)p->span)[2 * tid + 1];
-        in_span = r >= s0 && r <= s1;
-      }
-      if (in_span) {
-        const TD_GLOBAL float* bx = (const TD_GLOBAL float*)p->boxes + 4 * ((long long)r * p->K + tid);
-        const float c0 = bx[0], c1 = bx[1], c2 = bx[2], c3 = bx[3];
-        if (isfinite(c0) && isfinite(c1) && isfinite(c2) && isfinite(c3)) {
-          int x0 = round_coord(c0), y0 = round_coord(c1), x1 = round_coord(c2), y1 = round_coord(c3);
-          if (x1 > x0 && y1 > y0) {
-            const int mx = (int)(((long long)(x1 - x0) * p->margin_num) / p->margin_den), my = (int)(((long long)(y1 - y0) * p->margin_num) / p->margin_den);
-            const int wx0 = max(x0 - mx, 0), wx1 = min(x1 + mx, sw), wy0 = max(y0 - my, 0), wy1 = min(y1 + my, sh);
-            if (wx1 > wx0 && wy1 > wy0) {
-              if (mode == TD_REDACT_MOSAIC) {
-                const int cell = p->cell;
-                X0 = (wx0 / cell) * cell; X1 = min(((wx1 + cell - 1) / cell) * cell, sw);
-                Y0 = (wy0 / cell) * cell; Y1 = min(((wy1 + cell - 1) / cell) * cell, sh);
-              } else {
-                X0 = wx0 & ~1; X1 = min(wx1 + (wx1 & 1), sw);
-                Y0 = wy0 & ~1; Y1 = min(wy1 + (wy1 & 1), sh);
-              }
-            }
-          }
-        }
+    int x0, y0, x1, y1, wx0, wy0, cw, ch;
+    if (tid < p->K && r >= 0 && r < p->n_tube && row_in_span(p->span, tid, r) && rounded_box(p->boxes, (long long)r * p->K + tid, x0, y0, x1, y1) &&
+        grow_and_clamp(x0, y0, x1, y1, p->margin_num, p->margin_den, sh, sw, wx0, wy0, cw, ch)) {
+      const int wx1 = wx0 + cw, wy1 = wy0 + ch;
+      if (mode == TD_REDACT_MOSAIC) {  // step 6: whole cells, whole 2 x 2 blocks
+        const int cell = p->cell;
+        X0 = (wx0 / cell) * cell; X1 = min(((wx1 + cell - 1) / cell) * cell, sw);
+        Y0 = (wy0 / cell) * cell; Y1 = min(((wy1 + cell - 1) / cell) * cell, sh);
+      } else {
+        X0 = wx0 & ~1; X1 = min(wx1 + (wx1 & 1), sw);
+        Y0 = wy0 & ~1; Y1 = min(wy1 + (wy1 & 1), sh);
       }
     }
     rect[tid][0] = X0; rect[tid][1] = X1; rect[tid][2] = Y0; rect[tid][3] = Y1;
@@ -456,25 +392,15 @@ __global__ __launch_bounds__(kThreads) void tube_redact_kernel(const RedactParam
   }
 }
 
-namespace {
-
-struct Plane { const unsigned char* p; long long bytes; };
-
-size_t redact_table_bytes(int n_jobs) { return (((size_t)n_jobs * sizeof(RedactParams)) + 255) & ~(size_t)255; }
-
-}  // namespace
-
 }  // namespace td
 
 using namespace td;
 
-extern "C" size_t td_tube_redact_table_bytes(int n_jobs) { return n_jobs > 0 ? redact_table_bytes(n_jobs) : 0; }
+extern "C" size_t td_tube_redact_table_bytes(int n_jobs) { return table_bytes<RedactParams>(n_jobs); }
 
 extern "C" int td_tube_redact(const td_redact_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream) {
   const char* who = "td_tube_redact";
-  TD_REQUIRE(jobs && n_jobs > 0 && n_jobs <= 65536, "%s: no jobs (or more than 65536)", who);
-  TD_REQUIRE(table_host && table_dev && table_bytes >= td_tube_redact_table_bytes(n_jobs),
-             "%s: job-table workspace missing or smaller than td_tube_redact_table_bytes(%d)", who, n_jobs);
+  if (int rc = check_workspace<RedactParams>(who, jobs, n_jobs, table_host, table_dev, table_bytes)) return rc;
   RedactParams* host = (RedactParams*)table_host;
   int n = 0;
   long long blocks = 0;
@@ -492,46 +418,22 @@ extern "C" int td_tube_redact(const td_redact_job* jobs, int n_jobs, void* table
     TD_REQUIRE(j.mode != TD_REDACT_MOSAIC || (j.cell >= 2 && j.cell <= 256 && (j.cell & 1) == 0), "%s: job %d: cell = %d is not an even number in 2..256", who, i, j.cell);
     TD_REQUIRE(j.mode != TD_REDACT_BLUR || (j.radius >= 1 && j.radius <= 64), "%s: job %d: radius = %d outside 1..64", who, i, j.radius);
     TD_REQUIRE(j.boxes, "%s: job %d: boxes is null", who, i);
-    const int n_planes = j.fmt == TD_SRC_RGB24 ? 1 : j.fmt == TD_SRC_NV12 ? 2 : 3;
-    const int cw = (j.sw + 1) / 2, ch = (j.sh + 1) / 2;
-    const int row_bytes[3] = {j.fmt == TD_SRC_RGB24 ? 3 * j.sw : j.sw, j.fmt == TD_SRC_NV12 ? 2 * cw : cw, cw};
-    const int rows[3] = {j.sh, ch, ch}, cols[3] = {j.sw, cw, cw};
-    const void* sp[3] = {j.src0, j.src1, j.src2};
-    void* dp[3] = {j.dst0, j.dst1, j.dst2};
-    const int spitch[3] = {j.src_pitch0, j.src_pitch1, j.src_pitch2}, dpitch[3] = {j.dst_pitch0, j.dst_pitch1, j.dst_pitch2};
-    for (int k = 0; k < n_planes; k++) {
-      TD_REQUIRE(sp[k], "%s: job %d: src%d is null", who, i, k);
-      TD_REQUIRE(dp[k], "%s: job %d: dst%d is null", who, i, k);
-      TD_REQUIRE(spitch[k] >= row_bytes[k], "%s: job %d: src_pitch%d = %d is below its row of %d bytes", who, i, k, spitch[k], row_bytes[k]);
-      TD_REQUIRE(dpitch[k] >= row_bytes[k], "%s: job %d: dst_pitch%d = %d is below its row of %d bytes", who, i, k, dpitch[k], row_bytes[k]);
-      TD_REQUIRE(j.src_frame_stride >= (long long)spitch[k] * (rows[k] - 1) + row_bytes[k],
-                 "%s: job %d: src_frame_stride %lld is smaller than plane %d needs (%d rows of pitch %d)", who, i, j.src_frame_stride, k, rows[k], spitch[k]);
-      TD_REQUIRE(j.dst_frame_stride >= (long long)dpitch[k] * (rows[k] - 1) + row_bytes[k],
-                 "%s: job %d: dst_frame_stride %lld is smaller than plane %d needs (%d rows of pitch %d)", who, i, j.dst_frame_stride, k, rows[k], dpitch[k]);
-    }
-    // a destination plane is its source plane (refused for BLUR, whatever the frame count), or touches no source plane (byte ranges from
-    // the first row of frame 0 to the last row of frame T - 1; a job without frames has no bytes that could overlap)
-    const long long last = (long long)std::max(j.T - 1, 0);
-    Plane s[3], d[3];
-    for (int k = 0; k < n_planes; k++) {
-      s[k] = Plane{(const unsigned char*)sp[k], last * j.src_frame_stride + (long long)spitch[k] * (rows[k] - 1) + row_bytes[k]};
-      d[k] = Plane{(const unsigned char*)dp[k], last * j.dst_frame_stride + (long long)dpitch[k] * (rows[k] - 1) + row_bytes[k]};
-    }
+    const PlaneGeom g = plane_geom(j.fmt, j.sh, j.sw);
+    const PlaneSet sets[2] = {{"src", {j.src0, j.src1, j.src2}, {j.src_pitch0, j.src_pitch1, j.src_pitch2}, j.src_frame_stride},
+                              {"dst", {j.dst0, j.dst1, j.dst2}, {j.dst_pitch0, j.dst_pitch1, j.dst_pitch2}, j.dst_frame_stride}};
+    const PlaneSet &sp = sets[0], &dp = sets[1];
+    if (int rc = check_planes(who, i, g, sets, 2)) return rc;
     RedactParams p{};
-    for (int k = 0; k < n_planes; k++) {
-      if (dp[k] == sp[k] && dpitch[k] == spitch[k] && j.dst_frame_stride == j.src_frame_stride) {  // in place
-        TD_REQUIRE(j.mode != TD_REDACT_BLUR, "%s: job %d: dst%d is its source plane: TD_REDACT_BLUR cannot run in place (it reads neighbours that are already rewritten)", who, i, k);
-        p.inplace[k] = 1;
-        continue;
-      }
-      for (int m = 0; m < n_planes && j.T > 0; m++)
-        TD_REQUIRE(d[k].p + d[k].bytes <= s[m].p || s[m].p + s[m].bytes <= d[k].p,
-                   "%s: job %d: dst%d overlaps src%d without being the same plane (pointer, pitch and frame stride)", who, i, k, m);
+    for (int k = 0; k < g.n_planes; k++) {  // in place is refused for BLUR, whatever the frame count
+      bool inplace;
+      if (int rc = check_inplace_or_apart(who, i, g, sp, dp, j.T, k, &inplace)) return rc;
+      TD_REQUIRE(!inplace || j.mode != TD_REDACT_BLUR, "%s: job %d: dst%d is its source plane: TD_REDACT_BLUR cannot run in place (it reads neighbours that are already rewritten)", who, i, k);
+      p.inplace[k] = inplace;
     }
     if (j.T == 0) continue;
-    for (int k = 0; k < n_planes; k++) {
-      p.src[k] = (const unsigned char*)sp[k]; p.dst[k] = (unsigned char*)dp[k];
-      p.spitch[k] = spitch[k]; p.dpitch[k] = dpitch[k];
+    for (int k = 0; k < g.n_planes; k++) {
+      p.src[k] = (const unsigned char*)sp.p[k]; p.dst[k] = (unsigned char*)dp.p[k];
+      p.spitch[k] = sp.pitch[k]; p.dpitch[k] = dp.pitch[k];
     }
     p.sstride = j.src_frame_stride; p.dstride = j.dst_frame_stride;
     p.fmt = j.fmt; p.T = j.T; p.sh = j.sh; p.sw = j.sw;
@@ -540,10 +442,9 @@ extern "C" int td_tube_redact(const td_redact_job* jobs, int n_jobs, void* table
     p.margin_num = j.margin_num; p.margin_den = j.margin_den;
     p.cell = j.mode == TD_REDACT_MOSAIC ? j.cell : 2; p.radius = j.mode == TD_REDACT_BLUR ? j.radius : 1;
     p.color = (uint32_t)j.color[0] | ((uint32_t)j.color[1] << 8) | ((uint32_t)j.color[2] << 16);
-    p.n_planes = n_planes;
-    p.block_begin = (int)blocks;
+    p.n_planes = g.n_planes;
     long long job_blocks = 0;
-    for (int k = 0; k < n_planes; k++) {
+    for (int k = 0; k < g.n_planes; k++) {
       if (j.mode == TD_REDACT_MOSAIC && (k ? p.cell / 2 : p.cell) >= 2) {
         const int cp = k ? p.cell / 2 : p.cell;  // whole cells: about kBlurRows rows, at most kCols samples
         p.th[k] = cp * std::min(kMosaicCellRows, std::max(1, kBlurRows / cp));
@@ -556,21 +457,13 @@ extern "C" int td_tube_redact(const td_redact_job* jobs, int n_jobs, void* table
         p.th[k] = kFillRows;
         p.tw[k] = kFillCols;
       }
-      p.ntx[k] = cdiv(cols[k], p.tw[k]);
-      p.nty[k] = cdiv(rows[k], p.th[k]);
+      p.ntx[k] = cdiv(g.cols[k], p.tw[k]);
+      p.nty[k] = cdiv(g.rows[k], p.th[k]);
       p.pbegin[k] = (int)job_blocks;
       job_blocks += (long long)j.T * p.ntx[k] * p.nty[k];
-      TD_REQUIRE(blocks + job_blocks < (1LL << 31), "%s: too many workgroups", who);
     }
-    blocks += job_blocks;
+    if (int rc = add_blocks(who, blocks, job_blocks, p.block_begin)) return rc;
     host[n++] = p;
   }
-  if (n == 0) return TD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(table_dev, host, (size_t)n * sizeof(RedactParams), hipMemcpyHostToDevice, st) != hipSuccess) {
-    set_error("%s: job table upload failed", who);
-    return TD_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(tube_redact_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, (const RedactParams*)table_dev, n);
-  return check_launch(who);
+  return upload_and_launch(tube_redact_kernel, blocks, 0, host, table_dev, n, stream, who);
 }

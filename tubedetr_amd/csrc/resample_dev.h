@@ -1,30 +1,23 @@
 // Device code shared by the bilinear resampling kernels: td_clip_resample / td_clip_resample_src (augment.hip) and
 // td_tube_crop (tube_crop.hip).  The crop's pixels are DEFINED as what td_clip_resample writes for the same window, so the
 // three places where a bit could differ - the tap coordinates, the yuv -> rgb staging conversion and the order of the three
-// fmaf of the blend - exist once, here, and both translation units instantiate them.
+// fmaf of the blend - exist once, here, and both translation units instantiate them.  What these kernels share with the other
+// job-table kernels (addressing, the tube rule, plane checks, the launch) is in frame_jobs.h.
 //
 // The yuv functions are templates over the job record P; they read P's fields
 //   src, plane1, plane2 (plane pointers of frame 0), src_frame_stride, pitch, pitch1, pitch2, src_bytes, bytes1, bytes2 (extents),
 //   fmt, cmin (first staged source column), nd (staged Y dwords of a row), slot_bytes, yo, cy, crv, cgu, cgv, cbu.
 #pragma once
-#include "td_common.h"
+#include "frame_jobs.h"
 
 namespace td {
 
-constexpr int kThreads = 256;
 constexpr int kMaxBand = 4;        // output rows per workgroup
 constexpr int kStageDepth = 4;     // staged dwords per lane and source row held in registers (rows of up to 1365 pixels take the fast path)
 constexpr int kYuvDepth = 2;       // the same for Y dwords of an I420 / NV12 row (rows of up to 2045 pixels): a staged Y dword brings up to 4 chroma dwords along
 constexpr int kFrameChunk = 4;     // frames per workgroup (amortises the column table)
-constexpr int kMaxSide = 16384;    // (2x + 1) * sw stays below 2^30
 constexpr int kMaxSrcCols = 8192;  // 3 * (column - cmin) fits the table's 16-bit offsets
 constexpr size_t kMaxLds = 64 * 1024;
-
-// the table's pointers are loaded from memory, so the compiler cannot see that they are global: say so (global_load / global_store
-// instead of flat ones, which also occupy the LDS path that the taps need)
-#define TD_GLOBAL __attribute__((address_space(1)))
-typedef const TD_GLOBAL unsigned char* gcbyte_ptr;
-typedef TD_GLOBAL unsigned char* gbyte_ptr;
 
 struct ColEntry { unsigned short off0, off1; float w; };
 struct RowEntry { int y0, y1; float w; int pad; };

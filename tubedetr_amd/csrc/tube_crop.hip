@@ -17,6 +17,7 @@
 // band's first / last partial dword falls back to byte stores.  valid[t] and windows[t] are written by the workgroup of
 // band 0.  LDS: the column table is read at consecutive entries by consecutive lanes (8-byte entries: conflict-free per
 // half wave); the taps are byte reads of the staged rows at strides of the resampling ratio, as in clip_resample_kernel.
+// Steps 1 - 5 of the rule, the job search and the host's plane checks and launch are the family's: frame_jobs.h.
 #include <algorithm>
 
 #include "resample_dev.h"
@@ -51,37 +52,19 @@ struct CropParams {
 
 struct Window { int wy0, wx0, ch, cw, rh, rw; };  // all zero: the frame is empty
 
-__device__ __forceinline__ int round_coord(float v) { return (int)floorf(fminf(fmaxf(v, -1048576.f), 1048576.f) + 0.5f); }
-
 // the header's rule, steps 1 - 6, for frame t (uniform over the workgroup)
 __device__ __forceinline__ Window frame_window(const CropParams& p, int t) {
   Window w{0, 0, 0, 0, 0, 0};
-  const int r = p.frame_map ? ((const TD_GLOBAL int*)p.frame_map)[t] : t;
-  bool live = r >= 0 && r < p.n_tube;
-  if (live && p.span) {
-    const long long s0 = ((const TD_GLOBAL long long*)p.span)[0], s1 = ((const TD_GLOBAL long long*)p.span)[1];
-    live = r >= s0 && r <= s1;
-  }
-  if (live) {
-    const TD_GLOBAL float* bx = (const TD_GLOBAL float*)p.boxes + 4 * (long long)r;
-    const float c0 = bx[0], c1 = bx[1], c2 = bx[2], c3 = bx[3];
-    if (isfinite(c0) && isfinite(c1) && isfinite(c2) && isfinite(c3)) {
-      int x0 = round_coord(c0), y0 = round_coord(c1), x1 = round_coord(c2), y1 = round_coord(c3);
-      if (x1 > x0 && y1 > y0) {
-        const int mx = (int)(((long long)(x1 - x0) * p.margin_num) / p.margin_den), my = (int)(((long long)(y1 - y0) * p.margin_num) / p.margin_den);
-        x0 -= mx; x1 += mx; y0 -= my; y1 += my;
-        const int wx0 = max(x0, 0), wx1 = min(x1, p.sw), wy0 = max(y0, 0), wy1 = min(y1, p.sh);
-        const int cw = wx1 - wx0, ch = wy1 - wy0;
-        if (cw > 0 && ch > 0) {
-          int rh = p.oh, rw = p.ow;
-          if (p.keep_aspect) {
-            if ((long long)cw * p.oh >= (long long)ch * p.ow) rh = (int)min((long long)p.oh, max(1LL, (2LL * ch * p.ow + cw) / (2LL * cw)));
-            else rw = (int)min((long long)p.ow, max(1LL, (2LL * cw * p.oh + ch) / (2LL * ch)));
-          }
-          w = Window{wy0, wx0, ch, cw, rh, rw};
-        }
-      }
+  const int r = tube_row(p.frame_map, t);
+  int x0, y0, x1, y1, wx0, wy0, cw, ch;
+  if (r >= 0 && r < p.n_tube && row_in_span(p.span, 0, r) && rounded_box(p.boxes, r, x0, y0, x1, y1) &&
+      grow_and_clamp(x0, y0, x1, y1, p.margin_num, p.margin_den, p.sh, p.sw, wx0, wy0, cw, ch)) {
+    int rh = p.oh, rw = p.ow;
+    if (p.keep_aspect) {  // step 6
+      if ((long long)cw * p.oh >= (long long)ch * p.ow) rh = (int)min((long long)p.oh, max(1LL, (2LL * ch * p.ow + cw) / (2LL * cw)));
+      else rw = (int)min((long long)p.ow, max(1LL, (2LL * cw * p.oh + ch) / (2LL * ch)));
     }
+    w = Window{wy0, wx0, ch, cw, rh, rw};
   }
   w.wy0 = __builtin_amdgcn_readfirstlane(w.wy0); w.wx0 = __builtin_amdgcn_readfirstlane(w.wx0);
   w.ch = __builtin_amdgcn_readfirstlane(w.ch); w.cw = __builtin_amdgcn_readfirstlane(w.cw);
@@ -94,12 +77,7 @@ __device__ __forceinline__ Window frame_window(const CropParams& p, int t) {
 __global__ __launch_bounds__(kThreads) void tube_crop_kernel(const CropParams* __restrict__ tab, int n_jobs) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, b = blockIdx.x;
-  int lo = 0, hi = n_jobs - 1;
-  while (lo < hi) {  // last job whose first block is <= b (uniform: scalar loads)
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].block_begin <= b) lo = mid; else hi = mid - 1;
-  }
-  CropParams p = tab[lo];
+  CropParams p = tab[find_job(tab, n_jobs, b)];
   const int local = b - p.block_begin;
   const int band = local % p.nbands, chunk = local / p.nbands;
   const int yb = band * p.R;
@@ -238,10 +216,7 @@ __global__ __launch_bounds__(kThreads) void tube_crop_kernel(const CropParams* _
 
 namespace {
 
-size_t crop_table_bytes(int n_jobs) { return (((size_t)n_jobs * sizeof(CropParams)) + 255) & ~(size_t)255; }
-
 constexpr int kMaxOut = 4096;
-constexpr int kMaxMarginDen = 1024;
 
 }  // namespace
 
@@ -249,13 +224,11 @@ constexpr int kMaxMarginDen = 1024;
 
 using namespace td;
 
-extern "C" size_t td_tube_crop_table_bytes(int n_jobs) { return n_jobs > 0 ? crop_table_bytes(n_jobs) : 0; }
+extern "C" size_t td_tube_crop_table_bytes(int n_jobs) { return table_bytes<CropParams>(n_jobs); }
 
 extern "C" int td_tube_crop(const td_crop_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream) {
   const char* who = "td_tube_crop";
-  TD_REQUIRE(jobs && n_jobs > 0 && n_jobs <= 65536, "%s: no jobs (or more than 65536)", who);
-  TD_REQUIRE(table_host && table_dev && table_bytes >= td_tube_crop_table_bytes(n_jobs),
-             "%s: job-table workspace missing or smaller than td_tube_crop_table_bytes(%d)", who, n_jobs);
+  if (int rc = check_workspace<CropParams>(who, jobs, n_jobs, table_host, table_dev, table_bytes)) return rc;
   CropParams* host = (CropParams*)table_host;
   int n = 0;
   long long blocks = 0;
@@ -276,23 +249,14 @@ extern "C" int td_tube_crop(const td_crop_job* jobs, int n_jobs, void* table_hos
     TD_REQUIRE(j.keep_aspect == 0 || j.keep_aspect == 1, "%s: job %d: keep_aspect %d is not 0 or 1", who, i, j.keep_aspect);
     TD_REQUIRE(j.boxes, "%s: job %d: boxes is null", who, i);
     TD_REQUIRE(j.dst, "%s: job %d: dst is null", who, i);
-    const int n_planes = j.fmt == TD_SRC_RGB24 ? 1 : j.fmt == TD_SRC_NV12 ? 2 : 3;
-    const int cw = (j.sw + 1) / 2, ch = (j.sh + 1) / 2;
-    const int row_bytes[3] = {j.fmt == TD_SRC_RGB24 ? 3 * j.sw : j.sw, j.fmt == TD_SRC_NV12 ? 2 * cw : cw, cw};
-    const int rows[3] = {j.sh, ch, ch}, pitch[3] = {j.pitch0, j.pitch1, j.pitch2};
-    const void* planes[3] = {j.plane0, j.plane1, j.plane2};
-    for (int k = 0; k < n_planes; k++) {
-      TD_REQUIRE(planes[k], "%s: job %d: plane%d is null", who, i, k);
-      TD_REQUIRE(pitch[k] >= row_bytes[k], "%s: job %d: pitch%d = %d is below its row of %d bytes", who, i, k, pitch[k], row_bytes[k]);
-      TD_REQUIRE(j.frame_stride >= (long long)pitch[k] * (rows[k] - 1) + row_bytes[k],
-                 "%s: job %d: frame_stride %lld is smaller than plane %d needs (%d rows of pitch %d)", who, i, j.frame_stride, k, rows[k], pitch[k]);
-    }
+    const PlaneGeom g = plane_geom(j.fmt, j.sh, j.sw);
+    const PlaneSet src{"", {j.plane0, j.plane1, j.plane2}, {j.pitch0, j.pitch1, j.pitch2}, j.frame_stride};
+    if (int rc = check_planes(who, i, g, &src, 1)) return rc;
     if (j.T == 0) continue;
     CropParams p{};
-    const long long last = (long long)(j.T - 1) * j.frame_stride;
-    p.src = (const unsigned char*)j.plane0; p.pitch = j.pitch0; p.src_bytes = last + (long long)(rows[0] - 1) * pitch[0] + row_bytes[0];
-    if (n_planes > 1) { p.plane1 = (const unsigned char*)j.plane1; p.pitch1 = j.pitch1; p.bytes1 = last + (long long)(rows[1] - 1) * pitch[1] + row_bytes[1]; }
-    if (n_planes > 2) { p.plane2 = (const unsigned char*)j.plane2; p.pitch2 = j.pitch2; p.bytes2 = last + (long long)(rows[2] - 1) * pitch[2] + row_bytes[2]; }
+    p.src = (const unsigned char*)j.plane0; p.pitch = j.pitch0; p.src_bytes = plane_extent(g, 0, j.pitch0, j.frame_stride, j.T);
+    if (g.n_planes > 1) { p.plane1 = (const unsigned char*)j.plane1; p.pitch1 = j.pitch1; p.bytes1 = plane_extent(g, 1, j.pitch1, j.frame_stride, j.T); }
+    if (g.n_planes > 2) { p.plane2 = (const unsigned char*)j.plane2; p.pitch2 = j.pitch2; p.bytes2 = plane_extent(g, 2, j.pitch2, j.frame_stride, j.T); }
     p.src_frame_stride = j.frame_stride;
     p.fmt = j.fmt;
     if (j.fmt != TD_SRC_RGB24) {
@@ -312,17 +276,8 @@ extern "C" int td_tube_crop(const td_crop_job* jobs, int n_jobs, void* table_hos
     TD_REQUIRE(need <= kMaxLds, "%s: job %d needs %zu bytes of LDS: sw = %d and ow = %d are too large together", who, i, need, j.sw, j.ow);
     lds = std::max(lds, need);
     p.nbands = cdiv(j.oh, p.R);
-    p.block_begin = (int)blocks;
-    blocks += (long long)p.nbands * cdiv(j.T, kFrameChunk);
-    TD_REQUIRE(blocks < (1LL << 31), "%s: too many workgroups", who);
+    if (int rc = add_blocks(who, blocks, (long long)p.nbands * cdiv(j.T, kFrameChunk), p.block_begin)) return rc;
     host[n++] = p;
   }
-  if (n == 0) return TD_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(table_dev, host, (size_t)n * sizeof(CropParams), hipMemcpyHostToDevice, st) != hipSuccess) {
-    set_error("%s: job table upload failed", who);
-    return TD_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(tube_crop_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, st, (const CropParams*)table_dev, n);
-  return check_launch(who);
+  return upload_and_launch(tube_crop_kernel, blocks, lds, host, table_dev, n, stream, who);
 }

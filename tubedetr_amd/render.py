@@ -178,6 +178,14 @@ def _describe(base, sizes, tight, planes, pitches, frame_stride):
     return list(planes) + [None] * (3 - len(sizes)), pitches + [0] * (3 - len(sizes)), int(frame_stride)
 
 
+def _describe_src_dst(j, src, dst, sizes, tight, src_planes, src_pitches, src_frame_stride, dst_planes, dst_pitches, dst_frame_stride):
+    """The src* and dst* fields of an overlay or redact job; neither ``dst`` nor ``dst_planes``: in place."""
+    s = _describe(src, sizes, tight, src_planes, src_pitches, src_frame_stride)
+    d = s if dst is None and dst_planes is None else _describe(dst, sizes, tight, dst_planes, dst_pitches, dst_frame_stride)
+    (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride = s
+    (j.dst0, j.dst1, j.dst2), (j.dst_pitch0, j.dst_pitch1, j.dst_pitch2), j.dst_frame_stride = d
+
+
 def overlay_job(src: int, T: int, sh: int, sw: int, dst: Optional[int] = None, pix_fmt: str = "rgb24", boxes: Optional[int] = None, n_tube: int = 0,
                 span: Optional[int] = None, frame_map: Optional[int] = None, heat: Optional[int] = None, heat_hw: Tuple[int, int] = (0, 0),
                 box_color=(0xFA, 0xFF, 0x00), heat_color=(255, 0, 0), dim_color=(0, 0, 0), thickness: int = 2, heat_alpha: int = 0, dim_alpha: int = 0,
@@ -201,11 +209,7 @@ def overlay_job(src: int, T: int, sh: int, sw: int, dst: Optional[int] = None, p
         raise ValueError(f"n_tube = {n_tube} is negative")
     fmt, tight, sizes = _planes(pix_fmt, sh, sw)
     j = _hip.OverlayJob()
-    (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride = _describe(src, sizes, tight, src_planes, src_pitches, src_frame_stride)
-    if dst is None and dst_planes is None:
-        (j.dst0, j.dst1, j.dst2), (j.dst_pitch0, j.dst_pitch1, j.dst_pitch2), j.dst_frame_stride = (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride
-    else:
-        (j.dst0, j.dst1, j.dst2), (j.dst_pitch0, j.dst_pitch1, j.dst_pitch2), j.dst_frame_stride = _describe(dst, sizes, tight, dst_planes, dst_pitches, dst_frame_stride)
+    _describe_src_dst(j, src, dst, sizes, tight, src_planes, src_pitches, src_frame_stride, dst_planes, dst_pitches, dst_frame_stride)
     j.fmt, j.T, j.sh, j.sw = fmt, T, sh, sw
     j.boxes, j.span, j.frame_map, j.heat = boxes, span, frame_map, heat
     j.n_tube, j.mh, j.mw = int(n_tube), mh, mw
@@ -214,18 +218,31 @@ def overlay_job(src: int, T: int, sh: int, sw: int, dst: Optional[int] = None, p
     return j
 
 
+_JOB_TYPES = {"td_tube_overlay": "OverlayJob", "td_tube_crop": "CropJob", "td_tube_redact": "RedactJob"}  # entry point -> its record in _hip
+
+
+def _enqueue(entry: str, jobs: Sequence, host: torch.Tensor, dev: torch.Tensor, nbytes: int):
+    from . import _hip
+
+    arr = (getattr(_hip, _JOB_TYPES[entry]) * len(jobs))(*jobs)
+    _hip.check(getattr(_hip.lib(), entry)(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nbytes, _hip.stream_ptr()), entry)
+
+
+def _launch_fresh(entry: str, jobs: Sequence, device) -> tuple:
+    """tube_overlay / tube_crop / tube_redact: one launch on the current stream with freshly allocated job tables."""
+    from . import _hip
+
+    nb = int(getattr(_hip.lib(), entry + "_table_bytes")(len(jobs)))
+    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
+    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
+    _enqueue(entry, jobs, host, dev, nb)
+    return host, dev
+
+
 def tube_overlay(jobs: Sequence, device) -> tuple:
     """One td_tube_overlay launch on the current stream with freshly allocated job tables; returns them: the caller keeps
     them alive until the stream has passed the launch (``annotate`` recycles its own instead)."""
-    from . import _hip
-
-    lib = _hip.lib()
-    nb = int(lib.td_tube_overlay_table_bytes(len(jobs)))
-    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
-    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
-    arr = (_hip.OverlayJob * len(jobs))(*jobs)
-    _hip.check(lib.td_tube_overlay(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_tube_overlay")
-    return host, dev
+    return _launch_fresh("td_tube_overlay", jobs, device)
 
 
 # job tables of annotate(): (pinned, device, event recorded behind the launch).  A table is taken again only once its event has
@@ -239,6 +256,24 @@ def _take_table(nb: int, device):
             return _tables.pop(i)
     n = max(nb, 4096)
     return torch.empty(n, dtype=torch.uint8, pin_memory=True), torch.empty(n, dtype=torch.uint8, device=device), torch.cuda.Event()
+
+
+def _launch_pooled(entry: str, jobs: Sequence, keep: Sequence, results: list, single: bool, device):
+    """annotate / crop_tubes / redact: one launch on the current stream with a pooled job table; ``keep`` holds, per clip, the
+    tensors that the launch reads; returns ``results`` (its only entry for a single clip)."""
+    from . import _hip
+
+    nb = int(getattr(_hip.lib(), entry + "_table_bytes")(len(jobs)))
+    host, dev, ev = _take_table(nb, device)
+    _enqueue(entry, jobs, host, dev, host.numel())
+    ev.record()
+    _tables.append((host, dev, ev))
+    stream = torch.cuda.current_stream(device)
+    for group in keep:  # contiguous() may have made copies: the allocator must not hand them out before the launch has run
+        for t in group:
+            if t is not None:
+                t.record_stream(stream)
+    return results[0] if single else results
 
 
 def _as_list(v, n: int, name: str):
@@ -307,19 +342,7 @@ def annotate(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=No
                                 color_in_space(style.dim_color, *space), style.thickness, style.heat_alpha, style.dim_alpha))
         keep.append((b, s, h, m))
         results.append(o)
-    lib = _hip.lib()
-    nb = int(lib.td_tube_overlay_table_bytes(n))
-    host, dev, ev = _take_table(nb, device)
-    arr = (_hip.OverlayJob * n)(*jobs)
-    _hip.check(lib.td_tube_overlay(arr, n, host.data_ptr(), dev.data_ptr(), host.numel(), _hip.stream_ptr()), "td_tube_overlay")
-    ev.record()
-    _tables.append((host, dev, ev))
-    stream = torch.cuda.current_stream(device)
-    for group in keep:  # contiguous() may have made copies: the allocator must not hand them out before the launch has run
-        for t in group:
-            if t is not None:
-                t.record_stream(stream)
-    return results[0] if single else results
+    return _launch_pooled("td_tube_overlay", jobs, keep, results, single, device)
 
 
 # ---- grounded tubes cropped out of decoded frames (td_tube_crop, csrc/tube_crop.hip) ----------------------------------------
@@ -336,6 +359,13 @@ class TubeCrops(NamedTuple):
     windows: torch.Tensor  # int32 (T, 6): (wy0, wx0, ch, cw, rh, rw) - source window and resized size; zeros when not valid
 
 
+def _check_margin(num: int, den: int):
+    if not 1 <= den <= MAX_MARGIN_DEN:
+        raise ValueError(f"margin denominator {den}: 1..{MAX_MARGIN_DEN}")
+    if not 0 <= num <= 4 * den:
+        raise ValueError(f"margin {num}/{den}: between 0 and 4")
+
+
 def _crop_geometry(size, margin, keep_aspect):
     try:
         oh, ow = size
@@ -347,10 +377,7 @@ def _crop_geometry(size, margin, keep_aspect):
     oh, ow, num, den = int(oh), int(ow), int(num), int(den)
     if not (1 <= oh <= MAX_CROP_SIDE and 1 <= ow <= MAX_CROP_SIDE):
         raise ValueError(f"size {oh} x {ow}: sides in 1..{MAX_CROP_SIDE}")
-    if not 1 <= den <= MAX_MARGIN_DEN:
-        raise ValueError(f"margin denominator {den}: 1..{MAX_MARGIN_DEN}")
-    if not 0 <= num <= 4 * den:
-        raise ValueError(f"margin {num}/{den}: between 0 and 4")
+    _check_margin(num, den)
     if keep_aspect not in (0, 1, False, True):
         raise ValueError(f"keep_aspect {keep_aspect!r}: a bool")
     return oh, ow, num, den, int(bool(keep_aspect))
@@ -392,15 +419,7 @@ def crop_job(src: int, T: int, sh: int, sw: int, boxes: int, n_tube: int, dst: i
 def tube_crop(jobs: Sequence, device) -> tuple:
     """One td_tube_crop launch on the current stream with freshly allocated job tables; returns them: the caller keeps them
     alive until the stream has passed the launch (``crop_tubes`` recycles its own instead)."""
-    from . import _hip
-
-    lib = _hip.lib()
-    nb = int(lib.td_tube_crop_table_bytes(len(jobs)))
-    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
-    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
-    arr = (_hip.CropJob * len(jobs))(*jobs)
-    _hip.check(lib.td_tube_crop(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_tube_crop")
-    return host, dev
+    return _launch_fresh("td_tube_crop", jobs, device)
 
 
 def crop_tubes(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=None, frame_map=None, size: Tuple[int, int] = (224, 224),
@@ -445,19 +464,7 @@ def crop_tubes(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=
                              _hip.ptr(s), _hip.ptr(m), (num, den), bool(keep), mask.data_ptr(), valid.data_ptr(), windows.data_ptr()))
         keep_alive.append((c.data, b, s, m))
         results.append(TubeCrops(pixels, mask, valid, windows))
-    lib = _hip.lib()
-    nb = int(lib.td_tube_crop_table_bytes(n))
-    host, dev, ev = _take_table(nb, device)
-    arr = (_hip.CropJob * n)(*jobs)
-    _hip.check(lib.td_tube_crop(arr, n, host.data_ptr(), dev.data_ptr(), host.numel(), _hip.stream_ptr()), "td_tube_crop")
-    ev.record()
-    _tables.append((host, dev, ev))
-    stream = torch.cuda.current_stream(device)
-    for group in keep_alive:  # contiguous() may have made copies: the allocator must not hand them out before the launch has run
-        for t in group:
-            if t is not None:
-                t.record_stream(stream)
-    return results[0] if single else results
+    return _launch_pooled("td_tube_crop", jobs, keep_alive, results, single, device)
 
 
 # ---- grounded tubes redacted in decoded frames (td_tube_redact, csrc/redact.hip) ---------------------------------------------
@@ -479,10 +486,7 @@ def _redact_what(mode, cell, radius, margin, invert):
         raise ValueError(f"cell {cell}: an even number in 2..256")
     if mode == "blur" and not 1 <= radius <= 64:
         raise ValueError(f"radius {radius}: 1..64")
-    if not 1 <= den <= MAX_MARGIN_DEN:
-        raise ValueError(f"margin denominator {den}: 1..{MAX_MARGIN_DEN}")
-    if not 0 <= num <= 4 * den:
-        raise ValueError(f"margin {num}/{den}: between 0 and 4")
+    _check_margin(num, den)
     if invert not in (0, 1, False, True):
         raise ValueError(f"invert {invert!r}: a bool")
     return REDACT_MODES.index(mode), cell, radius, num, den, int(bool(invert))
@@ -510,11 +514,7 @@ def redact_job(src: int, T: int, sh: int, sw: int, boxes: int, n_tube: int, K: i
     code, cell, radius, num, den, inv = _redact_what(mode, cell, radius, margin, invert)
     fmt, tight, sizes = _planes(pix_fmt, sh, sw)
     j = _hip.RedactJob()
-    (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride = _describe(src, sizes, tight, src_planes, src_pitches, src_frame_stride)
-    if dst is None and dst_planes is None:
-        (j.dst0, j.dst1, j.dst2), (j.dst_pitch0, j.dst_pitch1, j.dst_pitch2), j.dst_frame_stride = (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride
-    else:
-        (j.dst0, j.dst1, j.dst2), (j.dst_pitch0, j.dst_pitch1, j.dst_pitch2), j.dst_frame_stride = _describe(dst, sizes, tight, dst_planes, dst_pitches, dst_frame_stride)
+    _describe_src_dst(j, src, dst, sizes, tight, src_planes, src_pitches, src_frame_stride, dst_planes, dst_pitches, dst_frame_stride)
     j.fmt, j.T, j.sh, j.sw = fmt, T, sh, sw
     j.boxes, j.span, j.frame_map = boxes, span, frame_map
     j.n_tube, j.K, j.mode, j.invert = n_tube, K, code, inv
@@ -526,15 +526,7 @@ def redact_job(src: int, T: int, sh: int, sw: int, boxes: int, n_tube: int, K: i
 def tube_redact(jobs: Sequence, device) -> tuple:
     """One td_tube_redact launch on the current stream with freshly allocated job tables; returns them: the caller keeps
     them alive until the stream has passed the launch (``redact`` recycles its own instead)."""
-    from . import _hip
-
-    lib = _hip.lib()
-    nb = int(lib.td_tube_redact_table_bytes(len(jobs)))
-    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
-    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
-    arr = (_hip.RedactJob * len(jobs))(*jobs)
-    _hip.check(lib.td_tube_redact(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_tube_redact")
-    return host, dev
+    return _launch_fresh("td_tube_redact", jobs, device)
 
 
 def redact(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=None, frame_map=None, mode: str = "mosaic", cell: int = 16, radius: int = 8,
@@ -592,16 +584,4 @@ def redact(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=None
                                color_in_space(color, c.pix_fmt, c.matrix, c.full_range), margin, invert))
         keep.append((c.data, b, s, m))
         results.append(o)
-    lib = _hip.lib()
-    nb = int(lib.td_tube_redact_table_bytes(n))
-    host, dev, ev = _take_table(nb, device)
-    arr = (_hip.RedactJob * n)(*jobs)
-    _hip.check(lib.td_tube_redact(arr, n, host.data_ptr(), dev.data_ptr(), host.numel(), _hip.stream_ptr()), "td_tube_redact")
-    ev.record()
-    _tables.append((host, dev, ev))
-    stream = torch.cuda.current_stream(device)
-    for group in keep:  # contiguous() may have made copies: the allocator must not hand them out before the launch has run
-        for t in group:
-            if t is not None:
-                t.record_stream(stream)
-    return results[0] if single else results
+    return _launch_pooled("td_tube_redact", jobs, keep, results, single, device)
