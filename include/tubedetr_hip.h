@@ -944,6 +944,88 @@ int td_conv_gemm_route(const td_conv_desc* d, const td_epilogue* e, int dtype, i
 /* has_a2: whether the launching call would pass a second source */
 int td_linear_ex_route(const td_linear_ex_desc* x, int has_a2, const td_epilogue* e, int dtype, int n_cu, td_gemm_route* routes, int* n_routes);
 
+/* ---- Grounded tubes interpolated to every decoded frame (an addition WITHIN ABI 11: nothing above changed) -------------
+ * The model answers at the sampled rate (one tube row per sampled frame); td_tube_overlay, td_tube_crop and td_tube_redact
+ * run on clips decoded at the full rate, and their frame_map can only HOLD the box of one tube row.  This stage turns the
+ * tube rows of many clips, in ONE launch, into one box per decoded frame - and optionally one attention map per decoded
+ * frame - which the three kernels then take with frame_map = NULL.  Per job:
+ *   Inputs, device pointers:
+ *     boxes      fp32 [n_tube][K][4], xyxy, required;
+ *     span       int64 [K][2]: first and last tube row of rectangle k, both inclusive (as in td_redact_job); NULL: every row;
+ *     row_frame  int32 [n_tube]: the frame number at which tube row r was sampled, increasing; NULL: row r sits at
+ *                first + r step.  Below, row_frame[r] means either;
+ *     heat       uint8 [n_tube][mh][mw]: one attention map per tube row; nullable.
+ *   Scalars: n_tube; K in 1..8; T dense frames; t0: dense frame i has frame number f = t0 + i (a long video can be done in
+ *     chunks); first, step (used without row_frame); mode = TD_DENSE_HOLD / TD_DENSE_LERP / TD_DENSE_HULL; smooth: a radius
+ *     in tube rows, 0..16; mh, mw (with heat).
+ *   Outputs, device pointers, each nullable except dense:
+ *     dense       fp32 [T][K][4];
+ *     valid       bytes [T][K];
+ *     dense_span  int64 [K][2];
+ *     dense_heat  uint8 [T][mh][mw]: required iff heat is given.
+ * The rule (this comment is the specification).  Every fp32 operation below is ONE IEEE operation rounded to nearest even,
+ * never contracted into a fused multiply-add, so numpy float32 reproduces it bit for bit; integers are exact.
+ *   1. Row r is PRESENT for rectangle k when span is NULL or span[k][0] <= r <= span[k][1], and the four coordinates of
+ *      boxes[r][k] are finite.
+ *   2. Smoothing.  With smooth = w > 0 the WORKING BOX of a present row r is, per coordinate, the fp32 sum over the present
+ *      rows q of [r - w, r + w] that lie in [0, n_tube), added in ascending q to +0.0f, divided once by (float)count.  Absent
+ *      rows stay absent.  With w = 0 the working box is the row's box, bits unchanged.
+ *   3. For dense frame i, f = t0 + i.  a is the largest r with row_frame[r] <= f and b = a + 1.
+ *        f < row_frame[0] or f > row_frame[n_tube - 1]: absent in every mode.
+ *        f == row_frame[a]: the working box of row a if it is present, else absent.  No arithmetic.
+ *        Otherwise fa = row_frame[a], fb = row_frame[b], num = f - fa, den = fb - fa; den <= 0 or den > 2^24 (a table that
+ *        does not increase, or does not keep the promise below): absent.
+ *      With a table, a is what this search returns, whatever the table holds: lo = 0, hi = n_tube - 1; while lo < hi:
+ *      mid = (lo + hi + 1) >> 1; row_frame[mid] <= f ? lo = mid : hi = mid - 1; a = lo.  No index leaves [0, n_tube).
+ *   4. Modes, for a frame strictly between row a and row b; A and B are their working boxes.
+ *        HOLD: A if a is present, else absent: what frame_map does today.
+ *        LERP: both present: wgt = (float)num / (float)den, v = A + wgt * (B - A) per coordinate: one division, one
+ *              subtraction, one multiplication, one addition, each rounded to fp32.  Otherwise absent.
+ *        HULL: both present: (min(A0, B0), min(A1, B1), max(A2, B2), max(A3, B3)), min(x, y) being y < x ? y : x and max(x, y)
+ *              y > x ? y : x.  Exactly one present: that row's working box.  Neither: absent.  The conservative cover for a
+ *              redaction: whatever moves in a straight line between two samples stays inside.
+ *   5. An absent (i, k) writes four quiet NaNs of bit pattern 0x7FC00000 and valid = 0; td_tube_overlay, td_tube_crop and
+ *      td_tube_redact treat a non-finite box as absent, so they need no span.  A computed box with a coordinate that is not
+ *      finite (an overflow) is written as computed, a NaN among them as 0x7FC00000, with valid = 0.  Otherwise valid = 1.
+ *   6. dense_span[k], in dense indices: s0 = max(span[k][0], 0), s1 = min(span[k][1], n_tube - 1) (NULL span: 0 and
+ *      n_tube - 1).  s0 > s1: (0, -1).  HOLD and LERP: (row_frame[s0] - t0, row_frame[s1] - t0).  HULL covers the open
+ *      intervals that its one-sided hold fills: the start is row_frame[s0 - 1] + 1 - t0 when s0 > 0, the end
+ *      row_frame[s1 + 1] - 1 - t0 when s1 < n_tube - 1.  Not clamped to [0, T): it is what td_overlay_job takes as span.
+ *   7. Heat, when given, for every byte of the map; it ignores span and smoothing.  Before the first or after the last row,
+ *      or a refused den: 0.  f == row_frame[a]: row a's byte qa.  In between, with qb row b's byte: HOLD: qa; LERP:
+ *      (qa (den - num) + qb num + den / 2) / den in integers; HULL: max(qa, qb).
+ * Refused on the host with a message that names the field (nothing is launched): boxes or dense NULL; n_tube < 1; K outside
+ * 1..8; T < 0 or T > 2^20; |t0| > 2^23; |first| > 2^23 and step outside 1..2^16 (both without row_frame only); smooth
+ * outside 0..16; an unknown mode; heat without dense_heat or the reverse; mh, mw outside 1..256 (with heat).  The frame
+ * numbers in row_frame are the caller's promise to lie within +-2^23: the int -> float conversions are then exact.  A job
+ * with T = 0 is legal and writes only dense_span.  `jobs` is a host array consumed before the call returns; the job table
+ * lives in caller-provided memory as for td_tube_overlay (table_host page-locked, table_dev device memory, both of
+ * td_tube_densify_table_bytes(n_jobs) bytes).  One launch for any number of jobs of mixed modes; no allocation, no
+ * synchronisation, no atomics: the same call returns the same bits.  No byte outside the job's outputs is written. */
+#define TD_DENSE_HOLD 0
+#define TD_DENSE_LERP 1
+#define TD_DENSE_HULL 2
+typedef struct td_dense_job {
+  const float* boxes;
+  const long long* span;
+  const int* row_frame;
+  const unsigned char* heat;
+  int n_tube;
+  int K;
+  int T;
+  int t0;
+  int first, step;
+  int mode;
+  int smooth;
+  int mh, mw;
+  float* dense;
+  unsigned char* valid;
+  long long* dense_span;
+  unsigned char* dense_heat;
+} td_dense_job;
+size_t td_tube_densify_table_bytes(int n_jobs);
+int td_tube_densify(const td_dense_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

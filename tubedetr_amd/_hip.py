@@ -113,6 +113,16 @@ class RedactJob(C.Structure):
                [(n, C.c_int) for n in ("n_tube", "K", "mode", "invert", "margin_num", "margin_den", "cell", "radius")] + [("color", C.c_ubyte * 3)]
 
 
+TD_DENSE_HOLD, TD_DENSE_LERP, TD_DENSE_HULL = 0, 1, 2
+
+
+class DenseJob(C.Structure):
+    """td_dense_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("boxes", "span", "row_frame", "heat")] + \
+               [(n, C.c_int) for n in ("n_tube", "K", "T", "t0", "first", "step", "mode", "smooth", "mh", "mw")] + \
+               [(n, C.c_void_p) for n in ("dense", "valid", "dense_span", "dense_heat")]
+
+
 class ReplicaMapsOut(C.Structure):
     """td_replica_maps_out."""
     _fields_ = [(n, C.c_void_p) for n in ("owner", "vid_of_frame", "vid_of_clip", "query_mask", "frame_dest", "clip_of", "vis_src", "vis_dst", "txt_src", "txt_dst",
@@ -198,6 +208,7 @@ _SIGS = {
     "td_sted_topk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "td_tube_crop": [C.POINTER(CropJob), _I, _P, _P, _SZ, _P],
     "td_tube_redact": [C.POINTER(RedactJob), _I, _P, _P, _SZ, _P],
+    "td_tube_densify": [C.POINTER(DenseJob), _I, _P, _P, _SZ, _P],
     "td_conv_gemm_route": [C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_linear_ex_route": [C.POINTER(LinearExDesc), _I, C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
 }
@@ -212,6 +223,7 @@ _SIZE_SIGS = {
     "td_tube_overlay_table_bytes": [_I],
     "td_tube_crop_table_bytes": [_I],
     "td_tube_redact_table_bytes": [_I],
+    "td_tube_densify_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],

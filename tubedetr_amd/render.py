@@ -1,6 +1,7 @@
 """Grounded tubes drawn into decoded frames on the device (td_tube_overlay, csrc/overlay.hip), cropped out of them
-(td_tube_crop, csrc/tube_crop.hip: ``crop_tubes``) and hidden in them (td_tube_redact, csrc/redact.hip: ``redact`` at the end
-of this file).
+(td_tube_crop, csrc/tube_crop.hip: ``crop_tubes``) and hidden in them (td_tube_redact, csrc/redact.hip: ``redact``); and, at
+the end of this file, the stage in front of the three: ``densify`` (td_tube_densify, csrc/tube_dense.hip) interpolates the tube
+rows, one per SAMPLED frame, to one box per DECODED frame.
 
 The reference shows an answer on the host: demo_stvg.py:152-194 and server_stvg.py:218-257 re-decode the video to JPEGs,
 open every frame in matplotlib, draw one rectangle and save the JPEG again.  Here the decoded frames stay on the device in
@@ -218,7 +219,7 @@ def overlay_job(src: int, T: int, sh: int, sw: int, dst: Optional[int] = None, p
     return j
 
 
-_JOB_TYPES = {"td_tube_overlay": "OverlayJob", "td_tube_crop": "CropJob", "td_tube_redact": "RedactJob"}  # entry point -> its record in _hip
+_JOB_TYPES = {"td_tube_overlay": "OverlayJob", "td_tube_crop": "CropJob", "td_tube_redact": "RedactJob", "td_tube_densify": "DenseJob"}  # entry point -> its record in _hip
 
 
 def _enqueue(entry: str, jobs: Sequence, host: torch.Tensor, dev: torch.Tensor, nbytes: int):
@@ -258,13 +259,17 @@ def _take_table(nb: int, device):
     return torch.empty(n, dtype=torch.uint8, pin_memory=True), torch.empty(n, dtype=torch.uint8, device=device), torch.cuda.Event()
 
 
-def _launch_pooled(entry: str, jobs: Sequence, keep: Sequence, results: list, single: bool, device):
-    """annotate / crop_tubes / redact: one launch on the current stream with a pooled job table; ``keep`` holds, per clip, the
-    tensors that the launch reads; returns ``results`` (its only entry for a single clip)."""
+def _launch_pooled(entry: str, jobs: Sequence, keep: Sequence, results: list, single: bool, device, tail_bytes: int = 0, fill_tail=None):
+    """annotate / crop_tubes / redact / densify: one launch on the current stream with a pooled job table; ``keep`` holds, per
+    clip, the tensors that the launch reads; returns ``results`` (its only entry for a single clip).  ``tail_bytes`` more bytes
+    of the pooled pair are handed to ``fill_tail(host_tail, dev_tail)`` before the launch: small host inputs of the jobs travel
+    in the table's memory and are guarded by its event."""
     from . import _hip
 
     nb = int(getattr(_hip.lib(), entry + "_table_bytes")(len(jobs)))
-    host, dev, ev = _take_table(nb, device)
+    host, dev, ev = _take_table(nb + tail_bytes, device)
+    if tail_bytes:
+        fill_tail(host[nb:nb + tail_bytes], dev[nb:nb + tail_bytes])
     _enqueue(entry, jobs, host, dev, host.numel())
     ev.record()
     _tables.append((host, dev, ev))
@@ -307,6 +312,7 @@ def annotate(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=No
       span       int64 (2,): the clip's row of ``sted_decode``'s output (first and last tube row with the object); None: all rows;
       heat       uint8 (n_tube, mh, mw) from ``heat_from_attention``; None: no attention overlay;
       frame_map  int32 (T,): the tube row of each frame (a clip decoded at full rate, a tube predicted at 5 fps); None: frame t is row t;
+                 (``densify`` gives such a clip one interpolated box, span and map per frame instead: pass them with frame_map = None;)
       out        ``DeviceFrames`` of the same geometry to write into; the clip itself: in place; None: a new buffer.
     Returns the annotated ``DeviceFrames`` (a list for a list).  Nothing here synchronises or copies to the host; ``style``'s
     RGB colours are converted to the frames' colour space by ``color_in_space``."""
@@ -428,7 +434,7 @@ def crop_tubes(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=
     ``frame_map`` are lists too, or None; the same clip may appear several times, once per tube).  Per clip:
       boxes      fp32 (n_tube, 4) xyxy in the frames' pixels on the device: what ``PostProcess`` returned for the clip, stacked;
       span       int64 (2,): the clip's row of ``sted_decode``'s output; frames outside it get no crop; None: all rows;
-      frame_map  int32 (T,): the tube row of each frame; None: frame t is row t.
+      frame_map  int32 (T,): the tube row of each frame; None: frame t is row t (``densify`` interpolates the boxes to every frame instead).
     ``size`` = (oh, ow) of every crop; ``margin`` = (num, den): context of num / den of the box side added on every side before
     the window is clamped to the frame; ``keep_aspect``: the window keeps its shape inside oh x ow (padded at the bottom /
     right, ``mask`` True there) instead of being stretched.  The rule is exact and stated in include/tubedetr_hip.h.
@@ -536,7 +542,7 @@ def redact(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=None
       boxes      fp32 (n_tube, 4) or (n_tube, K, 4) xyxy in the frames' pixels on the device: one tube, or the K <= 8 tubes of a
                  clip whose UNION is hidden in one pass;
       span       int64 (2,) or (K, 2): a row of ``sted_decode``'s output or a pick of ``moments_topk`` per tube; None: all rows;
-      frame_map  int32 (T,): the tube row of each frame; None: frame t is row t;
+      frame_map  int32 (T,): the tube row of each frame; None: frame t is row t (``densify(mode="hull")`` covers the frames between two rows instead);
       out        ``DeviceFrames`` of the same geometry to write into; the clip itself: in place (not for "blur"); None: a new buffer.
     ``mode``: "fill" (``color``, RGB, converted by ``color_in_space``), "mosaic" (``cell`` even, 2..256) or "blur" (a box mean of
     ``radius`` 1..64); ``margin`` = (num, den) grows every box by num / den of its side first.  The rule is exact and stated in
@@ -585,3 +591,173 @@ def redact(frames: Union[DeviceFrames, Sequence[DeviceFrames]], boxes, span=None
         keep.append((c.data, b, s, m))
         results.append(o)
     return _launch_pooled("td_tube_redact", jobs, keep, results, single, device)
+
+
+# ---- grounded tubes interpolated to every decoded frame (td_tube_densify, csrc/tube_dense.hip) -------------------------------
+DENSE_MODES = ("hold", "lerp", "hull")
+MAX_SMOOTH = 16
+MAX_DENSE_T = 1 << 20
+MAX_FRAME_NO = 1 << 23
+MAX_DENSE_STEP = 1 << 16
+
+
+class DenseTubes(NamedTuple):
+    """What ``densify`` returns for one clip: the tube at the decoded rate.  An absent box is four NaNs, which ``annotate``,
+    ``crop_tubes`` and ``redact`` take as "no box": pass ``boxes`` (and ``heat``) with frame_map = None."""
+    boxes: torch.Tensor           # fp32 (T, 4) or (T, K, 4)
+    span: torch.Tensor            # int64 (2,) or (K, 2): first and last dense frame of the span (``annotate``'s dim layer)
+    valid: torch.Tensor           # bool (T,) or (T, K): False where the box is absent or not finite
+    heat: Optional[torch.Tensor]  # uint8 (T, mh, mw), or None
+
+
+def _int_in(name: str, v, lo: int, hi: int) -> int:
+    try:
+        ok = not isinstance(v, bool) and int(v) == v and lo <= int(v) <= hi
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{name} = {v!r}: an integer in {lo}..{hi}")
+    return int(v)
+
+
+def _dense_what(T, t0, first, step, mode, smooth, has_table: bool):
+    if mode not in DENSE_MODES:
+        raise ValueError(f"mode {mode!r}: one of {DENSE_MODES}")
+    T, t0 = _int_in("T", T, 0, MAX_DENSE_T), _int_in("t0", t0, -MAX_FRAME_NO, MAX_FRAME_NO)
+    if has_table:
+        first, step = 0, 1
+    else:
+        first, step = _int_in("first", first, -MAX_FRAME_NO, MAX_FRAME_NO), _int_in("step", step, 1, MAX_DENSE_STEP)
+    return T, t0, first, step, DENSE_MODES.index(mode), _int_in("smooth", smooth, 0, MAX_SMOOTH)
+
+
+def dense_job(boxes: int, n_tube: int, T: int, dense: int, K: int = 1, span: Optional[int] = None, row_frame: Optional[int] = None, first: int = 0, step: int = 1,
+              t0: int = 0, heat: Optional[int] = None, heat_hw: Tuple[int, int] = (0, 0), mode: str = "lerp", smooth: int = 0, valid: Optional[int] = None,
+              dense_span: Optional[int] = None, dense_heat: Optional[int] = None):
+    """One ``td_dense_job``: the tube ``boxes`` (fp32 [n_tube][K][4]) sampled at the frame numbers ``row_frame`` (int32 [n_tube];
+    None: row r at first + r step) interpolated to the T frames t0 .. t0 + T - 1 into ``dense`` (fp32 [T][K][4]).  ``span`` (int64
+    [K][2]), ``heat`` (uint8 [n_tube][heat_hw[0]][heat_hw[1]]), ``valid`` (bytes [T][K]), ``dense_span`` (int64 [K][2]) and
+    ``dense_heat`` (uint8 [T][mh][mw], with ``heat``) are device addresses or None."""
+    from . import _hip
+
+    n_tube, K = int(n_tube), int(K)
+    T, t0, first, step, code, smooth = _dense_what(T, t0, first, step, mode, smooth, row_frame is not None)
+    if n_tube < 1:
+        raise ValueError(f"n_tube = {n_tube}: at least one tube row")
+    if not 1 <= K <= MAX_RECTS:
+        raise ValueError(f"K = {K}: 1..{MAX_RECTS} rectangles per tube row")
+    if not boxes or not dense:
+        raise ValueError("boxes and dense are device addresses, not None")
+    if (heat is None) != (dense_heat is None):
+        raise ValueError("heat and dense_heat come together")
+    mh, mw = int(heat_hw[0]), int(heat_hw[1])
+    if heat is not None and not (1 <= mh <= MAX_MAP and 1 <= mw <= MAX_MAP):
+        raise ValueError(f"token grid {mh} x {mw}: sides in 1..{MAX_MAP}")
+    j = _hip.DenseJob()
+    j.boxes, j.span, j.row_frame, j.heat = boxes, span, row_frame, heat
+    j.n_tube, j.K, j.T, j.t0, j.first, j.step, j.mode, j.smooth, j.mh, j.mw = n_tube, K, T, t0, first, step, code, smooth, mh, mw
+    j.dense, j.valid, j.dense_span, j.dense_heat = dense, valid, dense_span, dense_heat
+    return j
+
+
+def tube_densify(jobs: Sequence, device) -> tuple:
+    """One td_tube_densify launch on the current stream with freshly allocated job tables; returns them: the caller keeps
+    them alive until the stream has passed the launch (``densify`` recycles its own instead)."""
+    return _launch_fresh("td_tube_densify", jobs, device)
+
+
+def _per_clip(v, n: int, name: str, multi: bool):
+    """A scalar serves every clip; with a list of clips, a list or tuple gives one value each."""
+    if multi and isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError(f"{name}: {len(v)} entries for {n} clips")
+        return list(v)
+    return [v] * n
+
+
+def densify(boxes, T, row_frame=None, first=0, step=1, t0=0, span=None, heat=None, mode: str = "lerp", smooth=0):
+    """Interpolate grounded tubes from the sampled frames to every decoded frame: ONE launch for one clip or for a list of
+    clips (``boxes`` a list: ``row_frame``, ``span`` and ``heat`` are then lists too, or None, and ``T``, ``first``, ``step``,
+    ``t0``, ``mode`` and ``smooth`` may be lists or one value for all).  Per clip:
+      boxes      fp32 (n_tube, 4) or (n_tube, K, 4) xyxy on the device: what ``PostProcess`` returned, one row per sampled frame;
+      T, t0      dense frame i of T has frame number t0 + i (a long video is done in chunks);
+      row_frame  the frame number of every tube row, increasing: an int32 (n_tube,) tensor on the device, or a host sequence of
+                 integers (uploaded with the job table, asynchronously); None: row r was sampled at first + r * step;
+      span       int64 (2,) or (K, 2) tube rows, as ``redact`` takes them; None: all rows;
+      heat       uint8 (n_tube, mh, mw) from ``heat_from_attention``; None: no maps;
+      mode       "hold" (what a frame_map does), "lerp" (straight lines between two rows) or "hull" (the cover of both rows: for ``redact``);
+      smooth     a radius in tube rows, 0..16: every row becomes the mean of the present rows around it first.
+    The rule is exact - numpy float32 reproduces every bit - and stated in include/tubedetr_hip.h.  Returns ``DenseTubes`` (a
+    list for a list), whose boxes, span and heat go to ``annotate`` / ``crop_tubes`` / ``redact`` with frame_map = None.  Nothing
+    here synchronises or copies to the host, and bad arguments are refused before the device is touched."""
+    from . import _hip
+
+    multi = isinstance(boxes, (list, tuple))
+    clips = list(boxes) if multi else [boxes]
+    n = len(clips)
+    if n == 0:
+        return []
+    if multi:
+        frames_l, span_l, heat_l = (_as_list(v, n, k) for v, k in ((row_frame, "row_frame"), (span, "span"), (heat, "heat")))
+    else:
+        frames_l, span_l, heat_l = [row_frame], [span], [heat]
+    scalars = [_per_clip(v, n, k, multi) for v, k in ((T, "T"), (t0, "t0"), (first, "first"), (step, "step"), (mode, "mode"), (smooth, "smooth"))]
+    if not torch.is_tensor(clips[0]) or not clips[0].is_cuda:
+        # the scalars' refusals do not need a device: give them first, so that they are the same on a host without one
+        for i in range(n):
+            _dense_what(*(s[i] for s in scalars), has_table=frames_l[i] is not None)
+        raise ValueError("boxes: a torch.float32 tensor (n_tube, 4) or (n_tube, K, 4) on the device per clip")
+    device = clips[0].device
+    prepared, tail = [], 0
+    for i, (b, f, s, h) in enumerate(zip(clips, frames_l, span_l, heat_l)):  # every refusal comes before the first allocation and the launch
+        Ti, t0i, firsti, stepi, _, smoothi = _dense_what(*(sc[i] for sc in scalars), has_table=f is not None)
+        b = _dev_tensor(b, torch.float32, (4,), "boxes", device)
+        s = _dev_tensor(s, torch.int64, (2,), "span", device)
+        h = _dev_tensor(h, torch.uint8, (), "heat", device)
+        if b is None or b.dim() not in (2, 3) or b.shape[0] < 1:
+            raise ValueError("boxes (n_tube, 4) or (n_tube, K, 4) with n_tube >= 1")
+        n_tube, K = int(b.shape[0]), 1 if b.dim() == 2 else int(b.shape[1])
+        if not 1 <= K <= MAX_RECTS:
+            raise ValueError(f"boxes carry K = {K} rectangles per tube row: 1..{MAX_RECTS}")
+        if s is not None and not (s.dim() == 1 and K == 1 or s.dim() == 2 and s.shape[0] == K):
+            raise ValueError(f"span: (2,) for one tube, ({K}, 2) for {K}")
+        if h is not None and (h.dim() != 3 or h.shape[0] != n_tube or not (1 <= h.shape[1] <= MAX_MAP and 1 <= h.shape[2] <= MAX_MAP)):
+            raise ValueError(f"heat: uint8 ({n_tube}, mh, mw) with mh and mw in 1..{MAX_MAP}")
+        off = None
+        if torch.is_tensor(f):
+            f = _dev_tensor(f, torch.int32, (n_tube,), "row_frame", device)
+            if f.dim() != 1:
+                raise ValueError(f"row_frame: int32 ({n_tube},)")
+        elif f is not None:
+            f = [_int_in("row_frame entry", v, -MAX_FRAME_NO, MAX_FRAME_NO) for v in f]
+            if len(f) != n_tube:
+                raise ValueError(f"row_frame has {len(f)} entries for {n_tube} tube rows")
+            off, tail = tail, tail + (4 * n_tube + 15) // 16 * 16
+        prepared.append((b, f, s, h, off, n_tube, K, Ti, i))
+    jobs, keep, results, uploads = [], [], [], []
+    for b, f, s, h, off, n_tube, K, Ti, i in prepared:
+        dense = torch.empty(max(Ti, 1) * K * 4, dtype=torch.float32, device=device)[:Ti * K * 4]  # (T = 0 still has an address)
+        valid = torch.empty(max(Ti, 1) * K, dtype=torch.bool, device=device)[:Ti * K]
+        dspan = torch.empty((K, 2), dtype=torch.int64, device=device)
+        dheat = None
+        if h is not None:
+            mb = int(h.shape[1] * h.shape[2])
+            dheat = torch.empty(max(Ti, 1) * mb, dtype=torch.uint8, device=device)[:Ti * mb]
+        table = f if torch.is_tensor(f) else None
+        j = dense_job(b.data_ptr(), n_tube, Ti, dense.data_ptr(), K, _hip.ptr(s), _hip.ptr(table), scalars[2][i], scalars[3][i], scalars[1][i], _hip.ptr(h),
+                      tuple(h.shape[1:]) if h is not None else (0, 0), scalars[4][i], scalars[5][i], valid.data_ptr(), dspan.data_ptr(), _hip.ptr(dheat))
+        if off is not None:
+            uploads.append((j, off, f))
+        jobs.append(j)
+        keep.append((b, s, h, table))
+        one = b.dim() == 2
+        results.append(DenseTubes(dense.view(Ti, 4) if one else dense.view(Ti, K, 4), dspan.view(2) if one else dspan, valid.view(Ti) if one else valid.view(Ti, K),
+                                  dheat.view(Ti, h.shape[1], h.shape[2]) if h is not None else None))
+
+    def fill_tail(host_tail, dev_tail):
+        for j, off, values in uploads:
+            host_tail[off:off + 4 * len(values)].view(torch.int32).copy_(torch.tensor(values, dtype=torch.int32))
+            j.row_frame = dev_tail.data_ptr() + off
+        dev_tail.copy_(host_tail, non_blocking=True)
+
+    return _launch_pooled("td_tube_densify", jobs, keep, results, not multi, device, tail, fill_tail)
