@@ -1026,6 +1026,89 @@ typedef struct td_dense_job {
 size_t td_tube_densify_table_bytes(int n_jobs);
 int td_tube_densify(const td_dense_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
 
+/* ---- K labelled tubes and a moment timeline drawn in one pass (an addition WITHIN ABI 11: nothing above changed) ---------
+ * td_tube_overlay draws one tube in one colour, and two of its jobs cannot share destination frames.  This entry point draws
+ * the K <= 8 tubes of a clip (K sentences, or the K best moments of one) into the frames in ONE pass: every tube in its own
+ * colour with a label, and a timeline strip at the bottom that shows where the K spans lie and where the frame is.
+ * The frames side of a job - src0..2, dst0..2, pitches, frame strides, fmt, T, sh, sw, in place or apart, odd sizes - is
+ * td_overlay_job's, word for word: every byte of the rows of the job's destination frames gets the value defined below, no
+ * other byte is written and no byte outside the source rows is read.
+ * Inputs, device pointers, each nullable (NULL leaves its layers out):
+ *   boxes      fp32 [n_tube][K][4], xyxy in source pixels (td_redact_job's layout);
+ *   span       int64 [K][2]: first and last tube row of tube k, both inclusive; NULL: every row lies in every span;
+ *   frame_map  int32 [T], heat uint8 [n_tube][mh][mw], heat_alpha, heat_color, dim_alpha, dim_color, thickness, n_tube:
+ *              what they are in td_overlay_job;
+ *   tube_color[k]: the colour of tube k, tag_text_color, bar_color, cursor_color: three bytes IN THE FRAME'S OWN COLOUR SPACE;
+ *   tags       uint8 [K][tag_h][tag_w]: one alpha bitmap (a label) per tube, shared by all frames; needs boxes; with tag_h in
+ *              1..32, tag_w in 1..256, tag_scale in 1..8 (a bitmap sample covers tag_scale x tag_scale pixels) and tag_alpha
+ *              in [0, 256] (the plate under the label);
+ *   lane_h     0: no timeline; else 1..64, the height of a tube's lane; needs 1 <= n_tube <= 2^20 and K lane_h <= sh; with
+ *              bar_alpha and seg_alpha in [0, 256].
+ * The rule (exact integers, reproducible to the bit).  As in td_tube_overlay a frame is a stack of layers; a layer gives every
+ * luma pixel (rgb24: every pixel) an alpha a in [0, 256] and has ONE colour c, and a byte v becomes
+ * (v (256 - a) + c a + 128) >> 8.  r is the tube row of frame t (frame_map[t], or t).  A frame whose r is outside [0, n_tube) is
+ * a plain copy (no timeline either).  Else, in this order (a pixel outside a layer's area has a = 0 there):
+ *   1. dim, only when span is given and r lies outside EVERY tube's span: a = dim_alpha everywhere, c = dim_color.
+ *   2. heat, whenever heat is given: td_tube_overlay's step 2, word for word; c = heat_color.
+ *   3. box k, for k = 0 .. K - 1 in this order, only when boxes is given, r lies in span k (no span: always) and box
+ *      boxes[r][k] is present: its corners are rounded as in td_tube_overlay's step 3 (fp32, finite values clamped to +-2^20,
+ *      x0 = (int)floorf(bx0 + 0.5f), y0, x1, y1 alike; a non-finite coordinate, x1 <= x0 or y1 <= y0: absent).  a = 256 for a
+ *      pixel in [x0, x1) x [y0, y1) that is not in [x0 + th, x1 - th) x [y0 + th, y1 - th), c = tube_color[k].
+ *   4. tag k, for k = 0 .. K - 1 in this order, after ALL boxes, only where box k was drawn in step 3 and tags is given.  The
+ *      plate is PW = tag_w tag_scale pixels wide and PH = tag_h tag_scale high, at px0 = x0 and py0 = y0 - PH when that is
+ *      >= 0, else py0 = y0 (above the box; inside it when there is no room above).  Two layers on the pixels of
+ *      [px0, px0 + PW) x [py0, py0 + PH):
+ *        a. the plate: a = tag_alpha, c = tube_color[k];
+ *        b. the glyph: m = tags[k][(y - py0) / tag_scale][(x - px0) / tag_scale], a = (256 m + 127) / 255, c = tag_text_color.
+ *   5. the timeline, last, only when lane_h > 0: the strip is rows [sh - K lane_h, sh), lane k is rows
+ *      [sh - (K - k) lane_h, sh - (K - k - 1) lane_h), and column x stands for tube row i(x) = floor(x n_tube / sw) (64-bit).
+ *        a. the bar: a = bar_alpha on the whole strip, c = bar_color;
+ *        b. segment k, for k = 0 .. K - 1 in this order: a = seg_alpha on the pixels of lane k whose i(x) lies in span k (no
+ *           span: all of them), c = tube_color[k];
+ *        c. the cursor: a = 256 on columns [xc0, xc1) of the whole strip, xc0 = floor(r sw / n_tube),
+ *           xc1 = max(floor((r + 1) sw / n_tube), xc0 + 1), c = cursor_color.
+ * The parts of any layer outside the frame are simply absent.  A chroma sample (I420 / NV12) takes, PER LAYER, the mean alpha
+ * of the luma pixels of its 2 x 2 block that exist, (sum + n / 2) / n with n in {1, 2, 4}, and is blended with the U / V byte
+ * of that layer's colour - which is why the bar, each segment and the cursor are layers of their own.
+ * Two identities follow.  With K = 1, no tags, lane_h = 0 and tube_color[0] = box_color the result is td_tube_overlay's, byte
+ * for byte.  With no dim, heat, tags and timeline the result for K tubes is that of K in-place td_tube_overlay passes, k
+ * ascending, each with tube k's boxes, span and colour.
+ * Limits: td_overlay_job's, K in 1..8, and those named with the inputs above.  A violation returns an error whose message names
+ * the field; nothing is launched.  `jobs` is a host array consumed before the call returns; the job table lives in
+ * caller-provided memory as for td_tube_overlay (table_host page-locked, table_dev device memory, both of
+ * td_tube_overlay_multi_table_bytes(n_jobs) bytes).  One launch for any number of jobs of mixed formats and K; no allocation,
+ * no synchronisation inside. */
+typedef struct td_overlay_multi_job {
+  const void* src0; /* rgb24 pixels, or Y */
+  const void* src1; /* I420: U; NV12: UV pairs; RGB24: ignored */
+  const void* src2; /* I420: V; else ignored */
+  long long src_frame_stride;
+  int src_pitch0, src_pitch1, src_pitch2;
+  void* dst0;
+  void* dst1;
+  void* dst2;
+  long long dst_frame_stride;
+  int dst_pitch0, dst_pitch1, dst_pitch2;
+  int fmt;
+  int T, sh, sw;
+  const float* boxes;
+  const long long* span;
+  const int* frame_map;
+  const unsigned char* heat;
+  const unsigned char* tags;
+  int n_tube;
+  int K;
+  int mh, mw;
+  int thickness;
+  int heat_alpha, dim_alpha;
+  int tag_h, tag_w, tag_scale, tag_alpha;
+  int lane_h, bar_alpha, seg_alpha;
+  unsigned char tube_color[8][3];
+  unsigned char heat_color[3], dim_color[3], tag_text_color[3], bar_color[3], cursor_color[3];
+} td_overlay_multi_job;
+size_t td_tube_overlay_multi_table_bytes(int n_jobs);
+int td_tube_overlay_multi(const td_overlay_multi_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

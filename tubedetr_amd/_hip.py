@@ -95,6 +95,15 @@ class OverlayJob(C.Structure):
                [(n, C.c_int) for n in ("n_tube", "mh", "mw", "thickness", "heat_alpha", "dim_alpha")] + [(n, C.c_ubyte * 3) for n in ("box_color", "heat_color", "dim_color")]
 
 
+class OverlayMultiJob(C.Structure):
+    """td_overlay_multi_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("src0", "src1", "src2")] + [("src_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("src_pitch0", "src_pitch1", "src_pitch2")] + \
+               [(n, C.c_void_p) for n in ("dst0", "dst1", "dst2")] + [("dst_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("dst_pitch0", "dst_pitch1", "dst_pitch2")] + \
+               [(n, C.c_int) for n in ("fmt", "T", "sh", "sw")] + [(n, C.c_void_p) for n in ("boxes", "span", "frame_map", "heat", "tags")] + \
+               [(n, C.c_int) for n in ("n_tube", "K", "mh", "mw", "thickness", "heat_alpha", "dim_alpha", "tag_h", "tag_w", "tag_scale", "tag_alpha", "lane_h", "bar_alpha", "seg_alpha")] + \
+               [("tube_color", (C.c_ubyte * 3) * 8)] + [(n, C.c_ubyte * 3) for n in ("heat_color", "dim_color", "tag_text_color", "bar_color", "cursor_color")]
+
+
 class CropJob(C.Structure):
     """td_crop_job."""
     _fields_ = [(n, C.c_void_p) for n in ("plane0", "plane1", "plane2")] + [("frame_stride", C.c_longlong)] + \
@@ -209,6 +218,7 @@ _SIGS = {
     "td_tube_crop": [C.POINTER(CropJob), _I, _P, _P, _SZ, _P],
     "td_tube_redact": [C.POINTER(RedactJob), _I, _P, _P, _SZ, _P],
     "td_tube_densify": [C.POINTER(DenseJob), _I, _P, _P, _SZ, _P],
+    "td_tube_overlay_multi": [C.POINTER(OverlayMultiJob), _I, _P, _P, _SZ, _P],
     "td_conv_gemm_route": [C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_linear_ex_route": [C.POINTER(LinearExDesc), _I, C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
 }
@@ -224,6 +234,7 @@ _SIZE_SIGS = {
     "td_tube_crop_table_bytes": [_I],
     "td_tube_redact_table_bytes": [_I],
     "td_tube_densify_table_bytes": [_I],
+    "td_tube_overlay_multi_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],

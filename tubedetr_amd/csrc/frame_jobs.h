@@ -1,5 +1,5 @@
 // What the "job table" kernels on decoded frames share: td_clip_resample / td_clip_resample_src (augment.hip), td_tube_overlay
-// (overlay.hip), td_tube_crop (tube_crop.hip), td_tube_redact (redact.hip) and td_tube_densify (tube_dense.hip), the stage in front
+// (overlay.hip), td_tube_overlay_multi (overlay_multi.hip), td_tube_crop (tube_crop.hip), td_tube_redact (redact.hip) and td_tube_densify (tube_dense.hip), the stage in front
 // of the last three.  One launch serves a table of job records; a
 // workgroup finds its job by block_begin.  include/tubedetr_hip.h defines the crop's and the redaction's rectangles by reference
 // to the overlay's ("rounding is td_tube_overlay's", "the margin is td_tube_crop's step 4"): each step of that rule exists once,
@@ -106,6 +106,25 @@ __device__ __forceinline__ bool grow_and_clamp(int x0, int y0, int x1, int y1, i
   cw = min(x1 + mx, sw) - wx0; ch = min(y1 + my, sh) - wy0;
   return cw > 0 && ch > 0;
 }
+
+// ---- device: the overlays' pixel rule (td_tube_overlay, td_tube_overlay_multi) -------------------------------------------------
+// where column xl of the tile lives in the column table: the lanes of a wave read columns 16 apart (a luma run; 32 for an I420 chroma
+// run), which would all fall into 4 (2) of the 64 LDS banks; one spare slot per 16 columns makes the lane stride 17 (34) dwords
+__device__ __forceinline__ int col_slot(int xl) { return xl + (xl >> 4); }
+
+// kind of a byte row
+enum { kRgb = 0,      // 3 bytes per pixel
+       kLuma = 1,     // 1 byte per pixel
+       kChroma = 2,   // 1 byte per 2 x 2 block (I420: U, V, or both rows together)
+       kPairs = 3 };  // 2 bytes per block (NV12)
+
+__device__ __forceinline__ uint32_t blend(uint32_t v, uint32_t c, uint32_t a) { return (v * (256u - a) + c * a + 128u) >> 8; }
+
+// g = clamp(((2 v + 1) m 128) / n - 128, 0, 256 (m - 1))
+__device__ __forceinline__ int map_coord(int v, int m, int n) { return min(max(((2 * v + 1) * m * 128) / n - 128, 0), 256 * (m - 1)); }
+
+// a colour of a job record as the kernels carry it: byte k = component k
+inline uint32_t pack3(const unsigned char c[3]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16); }
 
 // ---- host: the planes of a job ----------------------------------------------------------------------------------------------
 // rgb24: one plane of 3 sw bytes per row; I420: Y, U, V; NV12: Y and the interleaved UV plane.  cols counts samples.

@@ -20,8 +20,8 @@
 //   * the blend (v (256 - a) + c a + 128) >> 8 cannot leave [0, 255], so there is no clamp here and nothing for the
 //     compiler to fuse into a packed shift-and-clamp (see shift_clamp_u8 in resample_dev.h before adding one).
 // The table's pointers are loaded from memory: they are declared global so that loads and stores are global_*, not flat_*
-// (which would also take the LDS path the tables need).  The job search, the byte runs, the steps of the box rule and the host's
-// plane checks and launch are the family's: frame_jobs.h.
+// (which would also take the LDS path the tables need).  The job search, the byte runs, the steps of the box rule, the blend and the
+// heat layer's map coordinate (shared with overlay_multi.hip) and the host's plane checks and launch are the family's: frame_jobs.h.
 #include "frame_jobs.h"
 
 namespace td {
@@ -51,21 +51,6 @@ struct OverlayParams {
 // column entry: bits 0-7 map column ix, 8-15 fraction fx, 16 inside [x0, x1), 17 inside [x0 + th, x1 - th)
 // row entry: bit 16, 17 alike for rows
 constexpr uint32_t kOuter = 1u << 16, kInner = 1u << 17;
-// where column xl of the tile lives in the column table: the lanes of a wave read columns 16 apart (a luma run; 32 for an I420 chroma
-// run), which would all fall into 4 (2) of the 64 LDS banks; one spare slot per 16 columns makes the lane stride 17 (34) dwords
-__device__ __forceinline__ int col_slot(int xl) { return xl + (xl >> 4); }
-
-// kind of a byte row
-enum { kRgb = 0,      // 3 bytes per pixel
-       kLuma = 1,     // 1 byte per pixel
-       kChroma = 2,   // 1 byte per 2 x 2 block (I420: U, V, or both rows together)
-       kPairs = 3 };  // 2 bytes per block (NV12)
-
-__device__ __forceinline__ uint32_t blend(uint32_t v, uint32_t c, uint32_t a) { return (v * (256u - a) + c * a + 128u) >> 8; }
-
-// g = clamp(((2 v + 1) m 128) / n - 128, 0, 256 (m - 1))
-__device__ __forceinline__ int map_coord(int v, int m, int n) { return min(max(((2 * v + 1) * m * 128) / n - 128, 0), 256 * (m - 1)); }
-
 struct Frame {  // what is uniform over a tile
   uint32_t a_dim;
   int heat_on, box_on, heat_alpha, mw;
@@ -245,12 +230,6 @@ __global__ __launch_bounds__(kThreads) void tube_overlay_kernel(const OverlayPar
     }
   }
 }
-
-namespace {
-
-uint32_t pack3(const unsigned char c[3]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16); }
-
-}  // namespace
 
 }  // namespace td
 
