@@ -144,8 +144,9 @@ int td_conv_wgrad(const void* g, const void* src, float* dw, const td_conv_desc*
 int td_conv_wgrad_bias(const void* g, const void* src, float* dw, float* dbias, const td_conv_desc* d, int ldg, int dtype,
                        int splits, td_stream_t stream);
 
-/* Batched weight gradients: ONE launch (two when 1x1 and 3x3 jobs are mixed) computes the weight gradients of many
- * conv layers.  dW of every job is written in the parameter's own [Nc][ci_real][R][S] fp32 layout with `scale[co]`
+/* Batched weight gradients: ONE call computes the weight gradients of many conv layers, in up to three launches per phase -
+ * one per kernel its jobs need (general geometry, pointwise, wide tiles) - and two phases (the overwriting jobs, then the
+ * `accumulate` jobs); td_conv_wgrad_batch_plan below returns the layout.  dW of every job is written in the parameter's own [Nc][ci_real][R][S] fp32 layout with `scale[co]`
  * (the FrozenBN factor, may be NULL) folded in - overwritten, not accumulated.  With thousands of output tiles in flight
  * a job needs no reduction splits (no atomics, no accumulator memset, no finalize pass) unless its M is very long.
  * A linear layer is a job with R=S=1 (dW = the parameter's [out][in]); its bias gradient rides along (`dbias`).  The
@@ -943,6 +944,41 @@ typedef struct td_gemm_route {
 int td_conv_gemm_route(const td_conv_desc* d, const td_epilogue* e, int dtype, int n_cu, td_gemm_route* routes, int* n_routes);
 /* has_a2: whether the launching call would pass a second source */
 int td_linear_ex_route(const td_linear_ex_desc* x, int has_a2, const td_epilogue* e, int dtype, int n_cu, td_gemm_route* routes, int* n_routes);
+
+/* ---- How a td_conv_wgrad_batch call would be laid out on the device (an addition WITHIN ABI 11: nothing above changed) ----
+ * td_conv_wgrad_batch plans the whole call with one host function - every argument check included - before it enqueues
+ * anything, and then launches the plan; this runs the same planner and returns the plan instead.  It touches no device (no HIP
+ * call; the jobs' pointers are only tested for NULL) and uses the process's TD_WGRAD_* knobs as a launch in the same process
+ * would; the CU count and the deterministic mode are arguments (the launching call passes the current device's and
+ * td_get_deterministic()).  plan_jobs[i] belongs to jobs[i]; `launches` has room for 6 records (3 kernels x 2 phases), in
+ * launch order.  An argument the launching call refuses is refused here with the same code and message. */
+#define TD_WGRAD_KERNEL_GENERAL 0   /* conv_wgrad_batch_kernel, any geometry */
+#define TD_WGRAD_KERNEL_POINTWISE 1 /* conv_wgrad_batch_kernel, 1x1 / stride 1 / no padding */
+#define TD_WGRAD_KERNEL_WIDE 2      /* conv_wgrad_wide_batch_kernel */
+typedef struct td_wgrad_plan_job {
+  int phase;               /* 0: overwriting, 1: accumulating (behind every launch of phase 0) */
+  int kernel;              /* TD_WGRAD_KERNEL_* */
+  int cls;                 /* wide tiles: bit 0 = 256 output channels per tile, bit 1 = 256 k columns, bit 2 = pointwise */
+  int tn, tk;              /* tile grid of the job */
+  int splits;              /* reduction splits: the job has tn * tk * splits work items */
+  int mper;                /* reduction rows per split */
+  int out_mode;            /* 2: plain stores (unsplit and overwriting), 1: fp32 atomics */
+  int fill_dw, fill_dbias; /* the library zero-fills dW / dbias ahead of the launches */
+  int xcd;                 /* the XCD whose workgroups run the job */
+  int first;               /* its first slot (work-item index) inside that XCD */
+  int launch;              /* index into `launches` */
+  int pos;                 /* row of the job in that launch's table */
+} td_wgrad_plan_job;
+typedef struct td_wgrad_plan_launch {
+  int phase, kernel, n_jobs;
+  int start[9];         /* table rows of XCD x: [start[x], start[x + 1]) */
+  int slots[8];         /* work items of XCD x */
+  unsigned grid, block; /* workgroups (8 x the longest XCD's slots), threads per workgroup */
+  int item_stages;      /* stages of 64 (bf16) / 32 (fp32) reduction rows a work item is bounded to */
+  double flops, bytes;  /* of the launch's jobs; the profiler records one row per phase, the sums over its launches */
+} td_wgrad_plan_launch;
+int td_conv_wgrad_batch_plan(const td_wgrad_job* jobs, int n_jobs, int dtype, int n_cu, int deterministic, td_wgrad_plan_job* plan_jobs,
+                             td_wgrad_plan_launch* launches, int* n_launches);
 
 /* ---- Grounded tubes interpolated to every decoded frame (an addition WITHIN ABI 11: nothing above changed) -------------
  * The model answers at the sampled rate (one tube row per sampled frame); td_tube_overlay, td_tube_crop and td_tube_redact

@@ -196,14 +196,11 @@ def test_trunk_weight_gradient_table_at_bench_shape():
     from tubedetr_amd import ops
 
     g = torch.Generator(device=dev()).manual_seed(9)
+    from wgrad_plan_cases import TRUNK_FRAMES, TRUNK_SHAPES
+
     Nb = FRAMES_BWD
-    # (Ci, H, W, Co, R, stride, pad)
-    shapes = [(256, 88, 88, 128, 1, 1, 0), (128, 88, 88, 128, 3, 2, 1), (128, 44, 44, 512, 1, 1, 0), (256, 88, 88, 512, 1, 2, 0),
-              (512, 44, 44, 128, 1, 1, 0), (128, 44, 44, 128, 3, 1, 1),
-              (512, 44, 44, 256, 1, 1, 0), (256, 44, 44, 256, 3, 2, 1), (256, 22, 22, 1024, 1, 1, 0), (512, 44, 44, 1024, 1, 2, 0),
-              (1024, 22, 22, 256, 1, 1, 0), (256, 22, 22, 256, 3, 1, 1),
-              (1024, 22, 22, 512, 1, 1, 0), (512, 22, 22, 512, 3, 2, 1), (512, 11, 11, 2048, 1, 1, 0), (1024, 22, 22, 2048, 1, 2, 0),
-              (2048, 11, 11, 512, 1, 1, 0), (512, 11, 11, 512, 3, 1, 1)]
+    assert Nb == TRUNK_FRAMES
+    shapes = TRUNK_SHAPES  # (Ci, H, W, Co, R, stride, pad); test_wgrad_plan_cpu.py plans the same list
     jobs, keep = [], []
     for i, (Ci, H, W, Co, R, st, pad) in enumerate(shapes):
         Ho, Wo = (H + 2 * pad - R) // st + 1, (W + 2 * pad - R) // st + 1
@@ -230,9 +227,10 @@ def test_wide_weight_gradient_tiles_at_their_smallest_ragged_shapes():
     from tubedetr_amd import ops
 
     g = torch.Generator(device=dev()).manual_seed(29)
-    N = 37
-    # (Ci, H, Co, R, stride, pad)
-    shapes = [(256, 22, 256, 3, 1, 1), (256, 22, 1024, 1, 1, 0), (1024, 22, 256, 1, 1, 0), (128, 44, 256, 3, 1, 1), (2048, 11, 512, 1, 1, 0)]
+    from wgrad_plan_cases import RAGGED_FRAMES, RAGGED_SHAPES
+
+    N = RAGGED_FRAMES  # 37
+    shapes = RAGGED_SHAPES  # (Ci, H, Co, R, stride, pad); test_wgrad_plan_cpu.py plans the same list
     jobs, refs = [], []
     for Ci, H, Co, R, st, pad in shapes:
         Ho = (H + 2 * pad - R) // st + 1

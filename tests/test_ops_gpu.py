@@ -35,17 +35,7 @@ def from_nhwc(y):
     return y.float().cpu().permute(0, 3, 1, 2)
 
 
-CONVS = [
-    # N, Cin, H, W, Cout, R, stride, pad
-    (2, 64, 12, 12, 64, 1, 1, 0),
-    (3, 64, 11, 13, 256, 1, 1, 0),
-    (2, 128, 14, 14, 128, 3, 1, 1),
-    (2, 128, 15, 13, 128, 3, 2, 1),
-    (2, 256, 9, 9, 512, 1, 2, 0),
-    (2, 8, 30, 34, 64, 7, 2, 3),
-    (1, 512, 6, 6, 2048, 1, 1, 0),
-    (5, 256, 22, 22, 256, 3, 1, 1),
-]
+from wgrad_plan_cases import AUTOGRAD_CFGS, CONVS, STEM_PADDED, WIDE_CFGS  # (N, Cin, H, W, Cout, R, stride, pad); test_wgrad_plan_cpu.py plans the same lists
 
 
 @pytest.mark.parametrize("dt", DT)
@@ -89,7 +79,7 @@ def test_conv_wgrad_batch_matches_autograd(dt):
     from tubedetr_amd import ops
 
     g = torch.Generator().manual_seed(21)
-    cfgs = CONVS + [(44, 64, 28, 28, 64, 1, 1, 0), (60, 64, 24, 24, 128, 3, 1, 1)]  # the last two are long enough to split (> 512 stages of 64 rows)
+    cfgs = AUTOGRAD_CFGS  # CONVS and two jobs long enough to split (> 512 stages of 64 rows)
     jobs, refs = [], []
     for i, (N, Ci, H, W, Co, R, st, pad) in enumerate(cfgs):
         x = rnd((N, Ci, H, W), g, dt)
@@ -105,6 +95,7 @@ def test_conv_wgrad_batch_matches_autograd(dt):
         assert got.shape == ref.shape
         assert rel_err(got, ref) < TOL[dt], cfg
     # padded source channels (the stem: 3 real channels stored as 8): only ci_real channels are written
+    assert STEM_PADDED == (2, 8, 30, 34, 64, 7, 2, 3)
     N, H, W, Co = 2, 30, 34, 64
     x = rnd((N, 3, H, W), g, dt)
     gy = rnd((N, Co, 15, 17), g, dt)
@@ -125,9 +116,7 @@ def test_conv_wgrad_batch_wide_tiles():
 
     dt = torch.bfloat16
     g = torch.Generator().manual_seed(23)
-    cfgs = [(8, 128, 28, 27, 128, 3, 1, 1), (52, 256, 26, 25, 256, 3, 1, 1), (5, 1024, 30, 31, 256, 1, 1, 0), (40, 512, 30, 30, 128, 1, 1, 0),
-            (6, 128, 28, 28, 512, 1, 1, 0), (8, 128, 57, 57, 128, 3, 2, 1), (2, 64, 12, 12, 64, 1, 1, 0), (3, 512, 40, 40, 512, 3, 1, 1),
-            (50, 128, 28, 27, 128, 3, 1, 1)]  # M = 33 800 / 36 000 / 37 800 rows: split in two (atomics), the others unsplit
+    cfgs = WIDE_CFGS  # M = 33 800 / 36 000 / 37 800 rows: split in two (atomics), the others unsplit
     jobs, refs = [], []
     for i, (N, Ci, H, W, Co, R, st, pad) in enumerate(cfgs):
         x = rnd((N, Ci, H, W), g, dt).to(dev())
@@ -145,6 +134,43 @@ def test_conv_wgrad_batch_wide_tiles():
     outs2 = ops.conv_wgrad_batch(jobs)  # stale outputs are overwritten, split jobs re-zeroed
     for a, b in zip(outs, outs2):
         assert rel_err(a, b) < 1e-5
+
+
+def test_conv_wgrad_batch_rejects_a_bad_job_before_anything_is_enqueued():
+    """Every argument check of td_conv_wgrad_batch is made by the planner, ahead of the first enqueue: job 0 is a valid pointwise job whose
+    12 544 rows make two splits at the 192-stage floor - so its dW gets a zero fill ahead of the launches - job 1 has ci_real = 0.  The call
+    returns TD_ERR_INVALID and job 0's dW still holds what was in it."""
+    import ctypes as C
+
+    import tubedetr_amd
+    from tubedetr_amd import _hip, ops
+
+    dt = torch.bfloat16
+    g = torch.randn(1, 112, 112, 8, device=dev()).to(dt)
+    x = torch.randn(1, 112, 112, 8, device=dev()).to(dt)
+    canary = torch.arange(64, dtype=torch.float32, device=dev()).view(8, 8, 1, 1) + 0.5
+    dw0, dw1 = canary.clone(), canary.clone()
+    arr = (_hip.WgradJob * 2)()
+    for a, dw in zip(arr, (dw0, dw1)):
+        a.g, a.src, a.dW, a.scale, a.dbias = g.data_ptr(), x.data_ptr(), dw.data_ptr(), None, None
+        a.d = ops._desc(1, 112, 112, 8, 112, 112, 1, 1, 1, 0, 0, 8, 8)
+        a.ldg, a.ci_real, a.accumulate, a.prezeroed = 8, 8, 0, 0
+    was = tubedetr_amd.is_deterministic()
+    try:
+        tubedetr_amd.set_deterministic(False)
+        (p0, _), _ = ops.conv_wgrad_batch_plan(arr, dt, torch.cuda.get_device_properties(0).multi_processor_count)
+        assert (p0.splits, p0.fill_dw) == (2, 1)  # the valid call would zero-fill job 0's dW
+        arr[1].ci_real = 0
+        nbytes = _hip.lib().td_conv_wgrad_batch_table_bytes(2)
+        th, td_, done = ops.job_tables.take(nbytes, dev())
+        rc = _hip.lib().td_conv_wgrad_batch(arr, 2, _hip.TD_BF16, th.data_ptr(), td_.data_ptr(), nbytes, _hip.stream_ptr())
+        msg = _hip.lib().td_last_error()
+        done()
+    finally:
+        tubedetr_amd.set_deterministic(was)
+    torch.cuda.synchronize()
+    assert rc == -1 and msg == b"td_conv_wgrad_batch: job 1: ci_real=0 out of range"  # TD_ERR_INVALID
+    assert torch.equal(dw0, canary) and torch.equal(dw1, canary)
 
 
 @pytest.mark.parametrize("dt", DT)

@@ -51,6 +51,18 @@ class GemmRoute(C.Structure):
                [(n, C.c_int) for n in ("dtype", "M", "N", "K", "R", "stride", "mode")]
 
 
+class WgradPlanJob(C.Structure):
+    """td_wgrad_plan_job."""
+    _fields_ = [(n, C.c_int) for n in ("phase", "kernel", "cls", "tn", "tk", "splits", "mper", "out_mode", "fill_dw", "fill_dbias", "xcd", "first", "launch", "pos")]
+
+
+class WgradPlanLaunch(C.Structure):
+    """td_wgrad_plan_launch."""
+    _fields_ = [(n, C.c_int) for n in ("phase", "kernel", "n_jobs")] + [("start", C.c_int * 9), ("slots", C.c_int * 8), ("grid", C.c_uint), ("block", C.c_uint),
+                                                                      ("item_stages", C.c_int), ("flops", C.c_double), ("bytes", C.c_double)]
+
+
+TD_WGRAD_KERNEL_GENERAL, TD_WGRAD_KERNEL_POINTWISE, TD_WGRAD_KERNEL_WIDE = 0, 1, 2
 TD_GEMM_KERNEL_TILED, TD_GEMM_KERNEL_PERSISTENT, TD_GEMM_KERNEL_BIG8, TD_GEMM_KERNEL_BIG8N = 0, 1, 2, 3
 TD_GEMM_WALK_POINTWISE, TD_GEMM_WALK_TAP_UNIFORM, TD_GEMM_WALK_GATHER, TD_GEMM_WALK_GX = 0, 1, 2, 3
 
@@ -221,6 +233,7 @@ _SIGS = {
     "td_tube_overlay_multi": [C.POINTER(OverlayMultiJob), _I, _P, _P, _SZ, _P],
     "td_conv_gemm_route": [C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_linear_ex_route": [C.POINTER(LinearExDesc), _I, C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
+    "td_conv_wgrad_batch_plan": [C.POINTER(WgradJob), _I, _I, _I, _I, C.POINTER(WgradPlanJob), C.POINTER(WgradPlanLaunch), C.POINTER(C.c_int)],
 }
 _SIZE_SIGS = {
     "td_grad_norm_ws_bytes": [],

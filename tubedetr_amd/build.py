@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtubedetr_hip.so")
-SOURCES = ["api.cpp", "gemm_conv.hip", "prep.hip", "elementwise.hip", "attention.hip", "resnet_exec.hip", "optim.hip", "criterion.hip", "stem.hip", "bottleneck.hip", "cross_attn.hip", "chain.hip", "augment.hip", "replica_maps.hip", "overlay.hip", "overlay_multi.hip", "moments.hip", "tube_crop.hip", "redact.hip", "tube_dense.hip"]
+SOURCES = ["api.cpp", "gemm_conv.hip", "conv_wgrad.hip", "prep.hip", "elementwise.hip", "attention.hip", "resnet_exec.hip", "optim.hip", "criterion.hip", "stem.hip", "bottleneck.hip", "cross_attn.hip", "chain.hip", "augment.hip", "replica_maps.hip", "overlay.hip", "overlay_multi.hip", "moments.hip", "tube_crop.hip", "redact.hip", "tube_dense.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
 
 
@@ -49,7 +49,8 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
     _check_compiler(hipcc)
-    headers = [os.path.join(CSRC, "td_common.h"), os.path.join(CSRC, "resample_dev.h"), os.path.join(CSRC, "frame_jobs.h"), os.path.join(CSRC, "gemm_route.h"),os.path.join(os.path.dirname(HERE), "include", "tubedetr_hip.h")]
+    headers = [os.path.join(CSRC, "td_common.h"), os.path.join(CSRC, "resample_dev.h"), os.path.join(CSRC, "frame_jobs.h"), os.path.join(CSRC, "gemm_route.h"), os.path.join(CSRC, "wgrad_plan.h"),
+               os.path.join(CSRC, "gemm_dev.h"), os.path.join(CSRC, "gemm_host.h"), os.path.join(os.path.dirname(HERE), "include", "tubedetr_hip.h")]
     objs, jobs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

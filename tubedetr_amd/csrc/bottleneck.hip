@@ -24,28 +24,12 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "td_common.h"
+#include "gemm_dev.h"
 
 namespace td {
 
-typedef __bf16 bn_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t bn_cvt_pk(float lo, float hi) {
-  bn_bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return *(uint32_t*)&v;
-}
-// ReLU of two packed bf16: as 16-bit integers, max(x, 0) (v_pk_max_i16) - a negative value (sign bit set, -0.0 included) becomes +0.0,
-// a non-negative one is unchanged.  ONE operation per two values behind the conversion; fmaxf(x, 0.f) before it is two per value
-// (the compiler quiets a possible signalling NaN with a v_max x, x first).
-// (As asm: written with vector types the compiler splits the conversion in front of it into two half conversions and a v_perm.  The
-// CONVERSION must stay the compiler's own instruction: it is the first reader of an MFMA result, and the wait states an MFMA -> VALU
-// read needs are inserted by the compiler's hazard pass, which does not look into asm operands - a v_cvt_pk_bf16_f32 written as
-// asm read accumulators the matrix pipe had not written yet.)
-__device__ __forceinline__ uint32_t bn_relu_pk(uint32_t v) {
-  uint32_t r;
-  asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(v));
-  return r;
-}
-__device__ __forceinline__ uint2 bn_relu_pack4(const f32x4& a) { return make_uint2(bn_relu_pk(bn_cvt_pk(a[0], a[1])), bn_relu_pk(bn_cvt_pk(a[2], a[3]))); }
+// (two fp32 -> packed bf16 and the ReLU of a packed pair: pack_bf16x2 / relu_bf16x2 of gemm_dev.h)
+__device__ __forceinline__ uint2 bn_relu_pack4(const f32x4& a) { return make_uint2(relu_bf16x2(pack_bf16x2(a[0], a[1])), relu_bf16x2(pack_bf16x2(a[2], a[3]))); }
 #ifndef TD_BN_XCD_CONTIG
 #define TD_BN_XCD_CONTIG 1  // an XCD's workgroups walk a contiguous range of tiles (0: tile = blockIdx + k * gridDim; A/B builds)
 #endif

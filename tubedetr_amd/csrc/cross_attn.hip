@@ -1278,7 +1278,7 @@ __global__ __launch_bounds__(512) void cross_q1_bwd_stream_mfma_kernel(CrossQ1Pa
 // layers' backward kernels left (k = 16 * layer + {ds[h], 8 + pd[h]}) and B row k = u_layer[h] or d_z_layer[h] - 10 x 16 output
 // tiles of v_mfma_f32_16x16x32_bf16 over KP / 32 k-steps.  C fragments are 16 contiguous bytes of a row (k along the lane's eight
 // values: the natural A operand); B is staged in LDS k-major as it lies in HBM and read with the transposing ds_read_b64_tr_b16
-// (the image and its 32-byte-block swizzle are the weight-gradient kernels': gemm_conv.hip wgrad_wide_body).  Wavefront w owns
+// (the image and its 32-byte-block swizzle are the weight-gradient kernels': conv_wgrad.hip wgrad_wide_body).  Wavefront w owns
 // channels 64 w .. 64 w + 63: its twelve B fragments live in registers across the row tiles; results go through a per-wavefront
 // LDS transposition so that every row is stored as 128 contiguous bytes.  One fp32-free pass writes the gradient in bf16.
 constexpr int DM_MAXL = 8;

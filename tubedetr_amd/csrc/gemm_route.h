@@ -36,7 +36,7 @@ struct GemmKnobs {
   int conv_big_persist = 1;    // TD_CONV_BIG_PERSIST (0 = one workgroup per tile)
   int conv_deep = 1;           // TD_CONV_DEEP
   int dgrad_s2_parity = 1;     // TD_DGRAD_S2_PARITY (0 = one gather over all 9 taps)
-  int wgrad_blocks = 256, wgrad_wide = 1, wgrad_wide_min_m = 4096, wgrad_split_stages = 0;  // TD_WGRAD_* (the weight-gradient host code)
+  int wgrad_blocks = 256, wgrad_wide = 1, wgrad_wide_min_m = 4096, wgrad_split_stages = 0;  // TD_WGRAD_* (wgrad_plan.h)
 };
 
 // a launch that uses a subset of the column blocks (filter taps) of a larger weight matrix

@@ -17,27 +17,13 @@
 
 #include <algorithm>
 
-#include "td_common.h"
+#include "gemm_dev.h"
 
 namespace td {
 
-typedef __bf16 bf16x2_v __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2_v __attribute__((ext_vector_type(2)));
 typedef unsigned int st_u32x4 __attribute__((ext_vector_type(4)));
-// two fp32 -> packed bf16 (v_cvt_pk_bf16_f32, round to nearest even)
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
-  bf16x2_v v = {(__bf16)lo, (__bf16)hi};
-  return *(uint32_t*)&v;
-}
-// ReLU of two packed bf16: max(x, 0) on the 16-bit integers (v_pk_max_i16): negative values, -0.0 included, become +0.0 - one operation
-// per pair behind the conversion (fmaxf(x, 0.f) in front of it is two per value).  As asm because the compiler splits the conversion
-// when it sees the vector form; the conversion itself must stay the compiler's instruction (it is the first reader of the MFMA result,
-// and the wait states that read needs are inserted by the compiler's hazard pass, which does not look into asm operands).
-__device__ __forceinline__ uint32_t relu_pk_bf16(uint32_t v) {
-  uint32_t r;
-  asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(v));
-  return r;
-}
+// (two fp32 -> packed bf16 and the ReLU of a packed pair: pack_bf16x2 / relu_bf16x2 of gemm_dev.h)
 // element-wise maximum of two packed pairs of NON-NEGATIVE bf16 values: their bit patterns order like unsigned integers (v_pk_max_u16)
 __device__ __forceinline__ uint32_t max_pk_nonneg_bf16(uint32_t a, uint32_t b) {
   const u16x2_v r = __builtin_elementwise_max(*(const u16x2_v*)&a, *(const u16x2_v*)&b);
@@ -152,8 +138,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(StemParams p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         uint2 o;  // (the integer ReLU leaves no -0.0, which would not order as an unsigned pattern in the pooling below)
-        o.x = relu_pk_bf16(cvt_pk_bf16(acc[i][0], acc[i][1])) & keep;
-        o.y = relu_pk_bf16(cvt_pk_bf16(acc[i][2], acc[i][3])) & keep;
+        o.x = relu_bf16x2(pack_bf16x2(acc[i][0], acc[i][1])) & keep;
+        o.y = relu_bf16x2(pack_bf16x2(acc[i][2], acc[i][3])) & keep;
         *(uint2*)(ctile + m * CPITCH + (i * 16 + 4 * lg) * 2) = o;
       }
     }

@@ -185,6 +185,14 @@ def conv_wgrad(g: Tensor, x: Tensor, R: int, S: int, stride: int, pad: int, *, o
     return dw
 
 
+def conv_wgrad_batch_plan(jobs, dtype: torch.dtype, n_cu: int, deterministic: bool = False):
+    """How td_conv_wgrad_batch would lay the ctypes array `jobs` of _hip.WgradJob out on a device of n_cu CUs: (one _hip.WgradPlanJob per job, one
+    _hip.WgradPlanLaunch per launch, in launch order).  No device is touched."""
+    pj, pl, n = (_hip.WgradPlanJob * len(jobs))(), (_hip.WgradPlanLaunch * 6)(), C.c_int(0)
+    check(_hip.lib().td_conv_wgrad_batch_plan(jobs, len(jobs), dtype_code(dtype), n_cu, int(deterministic), pj, pl, C.byref(n)), "td_conv_wgrad_batch_plan")
+    return list(pj), [pl[i] for i in range(n.value)]
+
+
 class _JobTables:
     """Caller-side staging of the job tables of td_conv_wgrad_batch / td_resnet_bwd (the C ABI allocates nothing): a
     ring of (page-locked host, device) buffer pairs.  An eager call recycles the pair used eight calls ago after its
@@ -235,7 +243,7 @@ job_tables = _JobTables()
 
 def conv_wgrad_batch(jobs) -> list:
     """jobs: iterable of (g NHWC [N,Ho,Wo,Co], x NHWC [N,H,W,C], R, S, stride, pad, scale [Co] fp32 | None, ci_real).
-    One launch (two when pointwise and spatial kernels are mixed); returns dW per job in the parameter layout
+    One call (its launches: conv_wgrad_batch_plan); returns dW per job in the parameter layout
     [Co, ci_real, R, S] fp32 with `scale` folded in."""
     jobs = list(jobs)
     arr = (_hip.WgradJob * len(jobs))()
