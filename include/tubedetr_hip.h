@@ -1145,6 +1145,110 @@ typedef struct td_overlay_multi_job {
 size_t td_tube_overlay_multi_table_bytes(int n_jobs);
 int td_tube_overlay_multi(const td_overlay_multi_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
 
+/* ---- Shot cuts in decoded frames (an addition WITHIN ABI 11: nothing above changed) -------------------------------------
+ * Every stage above takes a clip for one continuous take.  Across a hard cut td_tube_densify slides (LERP) or blows up (HULL)
+ * a box between two unrelated scenes.  Three entry points make the cuts visible: td_frame_stats reads the pixels once,
+ * td_shot_cuts decides on its statistics, td_tube_densify_shots stops at the result.  All of it is integers.
+ *
+ * td_frame_stats.  Per job (one clip):
+ *   src0..2, src_pitch0..2, src_frame_stride, fmt, T, sh, sw: the source side of td_overlay_job, word for word (every plane of
+ *     the format is described and checked, although the chroma planes are never read);
+ *   step in 1..8;
+ *   hist  uint32 [T][64], sad  uint32 [T]: device pointers, either nullable, not both.
+ * The rule (this comment is the specification):
+ *   The SAMPLED pixels are (y, x) with y % step == 0 and x % step == 0; N = ceil(sh / step) * ceil(sw / step) of them.
+ *   The luma L of a sampled pixel: I420 and NV12: the Y byte as stored, no range conversion; RGB24: (77 R + 150 G + 29 B + 128) >> 8.
+ *   hist[t][b] = the number of sampled pixels of frame t with L >> 2 == b.
+ *   sad[t]     = the sum over the sampled pixels of |L_t - L_(t-1)|; sad[0] = 0.  sad[t] == 0: frame t repeats frame t - 1.
+ * Refused on the host with a message that names the field (nothing is launched): an unknown fmt; T < 0; sh, sw outside
+ * 1..16384; sh * sw > 2^24 (which keeps sad below 2^32); step outside 1..8; hist and sad both NULL; every violation of a plane
+ * (null, pitch below the row, frame stride below the plane) in td_tube_overlay's words.  T = 0 is legal and writes nothing.
+ * One launch serves any number of jobs of mixed formats, sizes and steps.  The outputs are zeroed inside the call, on the
+ * stream, so the result does not depend on what they held; the sums are integer atomics, so the same call returns the same
+ * bits.  No allocation, no synchronisation, no byte outside the outputs is written.  A long video done in chunks overlaps
+ * them by ONE frame: sad of a chunk's first frame is 0 by definition, so the chunk behind starts at the last frame of the
+ * chunk in front and drops its own row 0.  Job table: as for td_tube_overlay, td_frame_stats_table_bytes(n_jobs) bytes. */
+typedef struct td_stats_job {
+  const void* src0; /* rgb24 pixels, or Y */
+  const void* src1; /* I420: U; NV12: UV pairs; RGB24: ignored */
+  const void* src2; /* I420: V; else ignored */
+  long long src_frame_stride;
+  int src_pitch0, src_pitch1, src_pitch2;
+  int fmt;
+  int T, sh, sw;
+  int step;
+  unsigned* hist;
+  unsigned* sad;
+} td_stats_job;
+size_t td_frame_stats_table_bytes(int n_jobs);
+int td_frame_stats(const td_stats_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
+/* td_shot_cuts consumes the statistics and touches no pixels.  Per job:
+ *   hist  uint32 [T][64], sad  uint32 [T]: what td_frame_stats wrote, both required; T in 0..2^20; N in 1..2^24, the number
+ *     of sampled pixels (every row of hist sums to it);
+ *   thresholds as integer fractions, numerators in 0..2^20, denominators in 1..2^20: hist_num / hist_den (the Python layer's
+ *     default: 1/4), sad_num / sad_den (8/1), peak_num / peak_den (3/1); w in 0..16 (4);
+ *   outputs, device pointers: d uint32 [T] (nullable), cut bytes [T], shot int32 [T], n_shots int32 [1].
+ * The rule.  d[0] = 0 and d[t] = sum_b |hist[t][b] - hist[t-1][b]| (uint32; at most 2 N).  Frame t >= 1 starts a new shot,
+ * cut[t] = 1, iff all four hold, in 64-bit integers:
+ *   1. d[t] * hist_den > hist_num * 2 N;
+ *   2. sad[t] * sad_den > sad_num * N;
+ *   3. d[t] is a local peak over the neighbours Q = {q != t : max(1, t - w) <= q <= min(T - 1, t + w)}: d[q] < d[t] for
+ *      q < t and d[q] <= d[t] for q > t.  Of equal neighbours the earliest wins: at most one cut per w + 1 frames;
+ *   4. Q is empty, or d[t] * peak_den * |Q| > peak_num * sum_{q in Q} d[q].
+ * Else cut[t] = 0; cut[0] = 0.  shot[t] = the inclusive prefix sum of cut; n_shots = shot[T - 1] + 1, or 0 for T = 0.
+ * Both gates are needed: the histogram gate alone fires on a fade, the difference gate alone on fast motion.  Known limit: a
+ * one-frame flash gives ONE cut, at its first frame (the frame behind it has an equal or lower d, and the earliest wins).  Gradual transitions
+ * are not cuts.  The defaults are starting values that were tried on synthetic clips only: no footage has validated them.
+ * Refused on the host, naming the field: hist, sad, cut, shot or n_shots NULL; T, N, w, a numerator or a denominator outside
+ * its range.  One workgroup per job, one launch for any number of jobs; no allocation, no synchronisation, no atomics. */
+typedef struct td_cuts_job {
+  const unsigned* hist;
+  const unsigned* sad;
+  int T;
+  int N;
+  int hist_num, hist_den;
+  int sad_num, sad_den;
+  int peak_num, peak_den;
+  int w;
+  unsigned* d;
+  unsigned char* cut;
+  int* shot;
+  int* n_shots;
+} td_cuts_job;
+size_t td_shot_cuts_table_bytes(int n_jobs);
+int td_shot_cuts(const td_cuts_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
+/* td_tube_densify_shots: td_tube_densify that stops at shot cuts.  jobs[i] is a td_dense_job, unchanged; shots[i] says which
+ * shot every frame number lies in:
+ *   shot     int32 [shot_T] on the device (td_shot_cuts' `shot`); NULL: no shots for this job;
+ *   shot_t0  the frame number of shot[0]; shot_T in 0..2^20.
+ * Frame number f has shot id shot[f - shot_t0] when 0 <= f - shot_t0 < shot_T; outside that range, or with shot NULL, its
+ * shot is UNKNOWN, which matches every shot.  So a caller densifying in chunks hands the whole video's array to every chunk,
+ * and chunked equals unchunked.  Two frame numbers are IN ONE SHOT when their shots match.
+ * The rule is td_tube_densify's, with these extensions (its step numbers):
+ *   1'. Row r is USABLE for frame f when it is present (step 1) and row_frame[r] and f are in one shot.
+ *   2'. The smoothing window of row r takes only the present rows q with row_frame[q] and row_frame[r] in one shot.
+ *   3', 4'. A frame on a row (f == row_frame[a]) is as before.  Strictly between rows a and b:
+ *        a and b both in one shot with f: step 4 as it stands (HULL's one-sided case included);
+ *        exactly one of them in one shot with f - a cut lies between f and the other: that row's working box if the row is
+ *          present, else absent, in EVERY mode (HOLD and LERP gain HULL's one-sided case at a cut);
+ *        neither (two cuts inside one interval, f between them): absent.
+ *      An absent row never becomes a one-sided hold in HOLD and LERP while its neighbour is in the same shot: with every
+ *      shot unknown the result is td_tube_densify's, bit for bit.
+ *   7'. Heat ignores presence as before: both rows in one shot with f: step 7; one: that row's byte; neither: 0.
+ *   dense_span (step 6) is unchanged.
+ * td_tube_densify IS this entry point with shots = NULL: one kernel.  `shots` may be NULL (then every job has none).  Refused:
+ * what td_tube_densify refuses, in its words but under this name, and shot_T outside 0..2^20 or |shot_t0| > 2^23 with a shot
+ * array.  The job table is td_tube_densify's: td_tube_densify_shots_table_bytes(n_jobs) == td_tube_densify_table_bytes(n_jobs) bytes. */
+typedef struct td_dense_shots {
+  const int* shot;
+  int shot_t0;
+  int shot_T;
+} td_dense_shots;
+size_t td_tube_densify_shots_table_bytes(int n_jobs);
+int td_tube_densify_shots(const td_dense_job* jobs, const td_dense_shots* shots, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

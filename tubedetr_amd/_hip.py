@@ -144,6 +144,24 @@ class DenseJob(C.Structure):
                [(n, C.c_void_p) for n in ("dense", "valid", "dense_span", "dense_heat")]
 
 
+class DenseShots(C.Structure):
+    """td_dense_shots."""
+    _fields_ = [("shot", C.c_void_p), ("shot_t0", C.c_int), ("shot_T", C.c_int)]
+
+
+class StatsJob(C.Structure):
+    """td_stats_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("src0", "src1", "src2")] + [("src_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("src_pitch0", "src_pitch1", "src_pitch2")] + \
+               [(n, C.c_int) for n in ("fmt", "T", "sh", "sw", "step")] + [(n, C.c_void_p) for n in ("hist", "sad")]
+
+
+class CutsJob(C.Structure):
+    """td_cuts_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("hist", "sad")] + \
+               [(n, C.c_int) for n in ("T", "N", "hist_num", "hist_den", "sad_num", "sad_den", "peak_num", "peak_den", "w")] + \
+               [(n, C.c_void_p) for n in ("d", "cut", "shot", "n_shots")]
+
+
 class ReplicaMapsOut(C.Structure):
     """td_replica_maps_out."""
     _fields_ = [(n, C.c_void_p) for n in ("owner", "vid_of_frame", "vid_of_clip", "query_mask", "frame_dest", "clip_of", "vis_src", "vis_dst", "txt_src", "txt_dst",
@@ -231,6 +249,9 @@ _SIGS = {
     "td_tube_redact": [C.POINTER(RedactJob), _I, _P, _P, _SZ, _P],
     "td_tube_densify": [C.POINTER(DenseJob), _I, _P, _P, _SZ, _P],
     "td_tube_overlay_multi": [C.POINTER(OverlayMultiJob), _I, _P, _P, _SZ, _P],
+    "td_frame_stats": [C.POINTER(StatsJob), _I, _P, _P, _SZ, _P],
+    "td_shot_cuts": [C.POINTER(CutsJob), _I, _P, _P, _SZ, _P],
+    "td_tube_densify_shots": [C.POINTER(DenseJob), C.POINTER(DenseShots), _I, _P, _P, _SZ, _P],
     "td_conv_gemm_route": [C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_linear_ex_route": [C.POINTER(LinearExDesc), _I, C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_conv_wgrad_batch_plan": [C.POINTER(WgradJob), _I, _I, _I, _I, C.POINTER(WgradPlanJob), C.POINTER(WgradPlanLaunch), C.POINTER(C.c_int)],
@@ -248,6 +269,9 @@ _SIZE_SIGS = {
     "td_tube_redact_table_bytes": [_I],
     "td_tube_densify_table_bytes": [_I],
     "td_tube_overlay_multi_table_bytes": [_I],
+    "td_frame_stats_table_bytes": [_I],
+    "td_shot_cuts_table_bytes": [_I],
+    "td_tube_densify_shots_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],

@@ -16,7 +16,10 @@
 //     rounding per operation, no fused multiply-add, which is what makes numpy float32 reproduce it;
 //   * the attention maps are byte work: a frame's map is one row of mh mw bytes, and a lane owns ALIGNED runs of 16 bytes of
 //     it (load_run / store_run of frame_jobs.h), loaded with one 16-byte load where the source row has the same alignment;
-//   * lanes 0 .. K - 1 of a job's first workgroup write dense_span; a job with T = 0 has that workgroup only.
+//   * lanes 0 .. K - 1 of a job's first workgroup write dense_span; a job with T = 0 has that workgroup only;
+//   * td_tube_densify_shots hands the job an array of shot ids by frame number.  A lane then looks up the shot of its frame and
+//     of rows a and b (and of every row of a smoothing window) in memory; a row on the other side of a cut drops out and its
+//     neighbour stands alone.  Without the array - td_tube_densify - no lookup is made and every branch goes as it did.
 // No atomics, no scratch; plain C++ and vector stores.  The job search, the span test, the byte runs, the workspace checks and
 // the launch are the family's: frame_jobs.h.
 #include "frame_jobs.h"
@@ -47,7 +50,17 @@ struct DenseParams {
   int map_bytes;  // mh mw; 0: no attention maps
   int fpb;        // dense frames per workgroup
   int block_begin;
+  const int* shot;  // td_tube_densify_shots: the shot of frame number shot_t0 + i, i < shot_T; null: no shots
+  int shot_t0, shot_T;
 };
+
+// the shot of frame number f; kAnyShot - unknown - outside the array: it matches every shot
+constexpr long long kAnyShot = 1LL << 40;
+__device__ __forceinline__ long long shot_of(const DenseParams* p, long long f) {
+  const long long i = f - p->shot_t0;
+  return i >= 0 && i < p->shot_T ? (long long)((const TD_GLOBAL int*)p->shot)[i] : kAnyShot;
+}
+__device__ __forceinline__ bool one_shot(long long x, long long y) { return x == y || x == kAnyShot || y == kAnyShot; }
 
 // the frame number of tube row r (0 <= r < n_tube)
 __device__ __forceinline__ long long row_frame_at(const DenseParams* p, const int* lds_table, int r) {
@@ -159,6 +172,7 @@ __global__ __launch_bounds__(kThreads) void tube_dense_kernel(const DenseParams*
   if (tid < nf * K) {
     const int fi = tid / K, k = tid - fi * K;
     const int a = fr_a[fi], num = fr_num[fi], den = fr_den[fi];
+    const bool shots = p->shot != nullptr;  // uniform
     auto present = [&](int r) -> bool {
       const int j = r - win_lo;
       return (j >= 0 && j < win_n) ? ((window[j] >> k) & 1) != 0 : present_in_memory(p, r, k);
@@ -174,8 +188,10 @@ __global__ __launch_bounds__(kThreads) void tube_dense_kernel(const DenseParams*
       }
       float s[4] = {0.f, 0.f, 0.f, 0.f};
       int count = 0;
+      const long long sr = shots ? shot_of(p, row_frame_at(p, lds_table, r)) : kAnyShot;
       for (int q = max(r - w, 0); q <= min(r + w, n - 1); q++) {
         if (!present(q)) continue;
+        if (shots && !one_shot(shot_of(p, row_frame_at(p, lds_table, q)), sr)) continue;
         const TD_GLOBAL float* bx = base + 4 * (long long)q * K;
 #pragma unroll
         for (int c = 0; c < 4; c++) s[c] = add_rn(s[c], bx[c]);
@@ -189,7 +205,15 @@ __global__ __launch_bounds__(kThreads) void tube_dense_kernel(const DenseParams*
     bool have = false;
     if (den > 0) {
       const bool pa = present(a);
-      if (num == 0 || mode == TD_DENSE_HOLD) {
+      bool ia = true, ib = true;  // rows a and b are in one shot with the frame
+      if (shots && num != 0) {
+        const long long sf = shot_of(p, (long long)p->t0 + i0 + fi);
+        ia = one_shot(shot_of(p, row_frame_at(p, lds_table, a)), sf);
+        ib = one_shot(shot_of(p, row_frame_at(p, lds_table, a + 1)), sf);
+      }
+      if (!(ia && ib)) {  // a cut between the frame and a row: the other row alone, in every mode
+        if (ia ? pa : (ib && present(a + 1))) { working(ia ? a : a + 1, v); have = true; }
+      } else if (num == 0 || mode == TD_DENSE_HOLD) {
         if (pa) { working(a, v); have = true; }
       } else {
         const bool pb = present(a + 1);
@@ -241,7 +265,15 @@ __global__ __launch_bounds__(kThreads) void tube_dense_kernel(const DenseParams*
     const int v0 = max(o0, 0), v1 = min(o0 + kRun, mb);
     const int a = fr_a[fi], num = fr_num[fi], den = fr_den[fi];
     uint32_t out[4] = {0, 0, 0, 0};
-    if (den > 0) {
+    bool ia = true, ib = true;
+    if (p->shot && den > 0 && num != 0) {
+      const long long sf = shot_of(p, (long long)p->t0 + i0 + fi);
+      ia = one_shot(shot_of(p, row_frame_at(p, lds_table, a)), sf);
+      ib = one_shot(shot_of(p, row_frame_at(p, lds_table, a + 1)), sf);
+    }
+    if (den > 0 && !(ia && ib)) {  // a cut between the frame and a row: the other row's bytes, or none
+      if (ia || ib) load_run(p->heat + (long long)(ia ? a : a + 1) * mb, o0, v0, v1, out);
+    } else if (den > 0) {
       const unsigned char* ra = p->heat + (long long)a * mb;
       load_run(ra, o0, v0, v1, out);
       if (num != 0 && mode != TD_DENSE_HOLD) {
@@ -265,8 +297,8 @@ using namespace td;
 
 extern "C" size_t td_tube_densify_table_bytes(int n_jobs) { return table_bytes<DenseParams>(n_jobs); }
 
-extern "C" int td_tube_densify(const td_dense_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream) {
-  const char* who = "td_tube_densify";
+// td_tube_densify is td_tube_densify_shots without shots: one list of checks, one kernel
+static int densify(const char* who, const td_dense_job* jobs, const td_dense_shots* shots, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream) {
   if (int rc = check_workspace<DenseParams>(who, jobs, n_jobs, table_host, table_dev, table_bytes)) return rc;
   DenseParams* host = (DenseParams*)table_host;
   int n = 0;
@@ -288,8 +320,14 @@ extern "C" int td_tube_densify(const td_dense_job* jobs, int n_jobs, void* table
     TD_REQUIRE(!j.heat || j.dense_heat, "%s: job %d: heat is given but dense_heat is null", who, i);
     TD_REQUIRE(!j.dense_heat || j.heat, "%s: job %d: dense_heat is given but heat is null", who, i);
     if (j.heat) TD_REQUIRE(j.mh >= 1 && j.mh <= kMaxMap && j.mw >= 1 && j.mw <= kMaxMap, "%s: job %d: mh x mw = %d x %d outside 1..%d", who, i, j.mh, j.mw, kMaxMap);
+    const bool with_shots = shots && shots[i].shot;
+    if (with_shots) {
+      TD_REQUIRE(shots[i].shot_T >= 0 && shots[i].shot_T <= kMaxT, "%s: job %d: shot_T = %d outside 0..%d", who, i, shots[i].shot_T, kMaxT);
+      TD_REQUIRE(shots[i].shot_t0 >= -kMaxFrameNo && shots[i].shot_t0 <= kMaxFrameNo, "%s: job %d: shot_t0 = %d outside +-%d", who, i, shots[i].shot_t0, kMaxFrameNo);
+    }
     if (j.T == 0 && !j.dense_span) continue;
     DenseParams p{};
+    if (with_shots) { p.shot = shots[i].shot; p.shot_t0 = shots[i].shot_t0; p.shot_T = shots[i].shot_T; }
     p.boxes = j.boxes; p.span = j.span; p.row_frame = j.row_frame; p.heat = j.heat;
     p.dense = j.dense; p.valid = j.valid; p.dense_span = j.dense_span; p.dense_heat = j.dense_heat;
     p.n_tube = j.n_tube; p.K = j.K; p.T = j.T; p.t0 = j.t0; p.mode = j.mode; p.smooth = j.smooth;
@@ -301,4 +339,14 @@ extern "C" int td_tube_densify(const td_dense_job* jobs, int n_jobs, void* table
     host[n++] = p;
   }
   return upload_and_launch(tube_dense_kernel, blocks, 0, host, table_dev, n, stream, who);
+}
+
+extern "C" int td_tube_densify(const td_dense_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream) {
+  return densify("td_tube_densify", jobs, nullptr, n_jobs, table_host, table_dev, table_bytes, stream);
+}
+
+extern "C" size_t td_tube_densify_shots_table_bytes(int n_jobs) { return table_bytes<DenseParams>(n_jobs); }
+
+extern "C" int td_tube_densify_shots(const td_dense_job* jobs, const td_dense_shots* shots, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream) {
+  return densify("td_tube_densify_shots", jobs, shots, n_jobs, table_host, table_dev, table_bytes, stream);
 }

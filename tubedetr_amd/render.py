@@ -2,7 +2,8 @@
 timeline in one pass: td_tube_overlay_multi, csrc/overlay_multi.hip: ``annotate_tubes``), cropped out of them
 (td_tube_crop, csrc/tube_crop.hip: ``crop_tubes``) and hidden in them (td_tube_redact, csrc/redact.hip: ``redact``); and, at
 the end of this file, the stage in front of the three: ``densify`` (td_tube_densify, csrc/tube_dense.hip) interpolates the tube
-rows, one per SAMPLED frame, to one box per DECODED frame.
+rows, one per SAMPLED frame, to one box per DECODED frame, and ``frame_stats`` / ``shot_cuts`` (td_frame_stats, td_shot_cuts,
+csrc/frame_stats.hip) find the hard cuts in the frames, at which ``densify(shots=...)`` (td_tube_densify_shots) stops.
 
 The reference shows an answer on the host: demo_stvg.py:152-194 and server_stvg.py:218-257 re-decode the video to JPEGs,
 open every frame in matplotlib, draw one rectangle and save the JPEG again.  Here the decoded frames stay on the device in
@@ -221,7 +222,7 @@ def overlay_job(src: int, T: int, sh: int, sw: int, dst: Optional[int] = None, p
 
 
 _JOB_TYPES = {"td_tube_overlay": "OverlayJob", "td_tube_overlay_multi": "OverlayMultiJob", "td_tube_crop": "CropJob", "td_tube_redact": "RedactJob",
-              "td_tube_densify": "DenseJob"}  # entry point -> its record in _hip
+              "td_tube_densify": "DenseJob", "td_frame_stats": "StatsJob", "td_shot_cuts": "CutsJob"}  # entry point -> its record in _hip
 
 
 def _enqueue(entry: str, jobs: Sequence, host: torch.Tensor, dev: torch.Tensor, nbytes: int):
@@ -261,18 +262,22 @@ def _take_table(nb: int, device):
     return torch.empty(n, dtype=torch.uint8, pin_memory=True), torch.empty(n, dtype=torch.uint8, device=device), torch.cuda.Event()
 
 
-def _launch_pooled(entry: str, jobs: Sequence, keep: Sequence, results: list, single: bool, device, tail_bytes: int = 0, fill_tail=None):
+def _launch_pooled(entry: str, jobs: Sequence, keep: Sequence, results: list, single: bool, device, tail_bytes: int = 0, fill_tail=None, enqueue=None):
     """annotate / crop_tubes / redact / densify: one launch on the current stream with a pooled job table; ``keep`` holds, per
     clip, the tensors that the launch reads; returns ``results`` (its only entry for a single clip).  ``tail_bytes`` more bytes
     of the pooled pair are handed to ``fill_tail(host_tail, dev_tail)`` before the launch: small host inputs of the jobs travel
-    in the table's memory and are guarded by its event."""
+    in the table's memory and are guarded by its event.  ``enqueue(host, dev, nbytes)`` replaces the plain call of ``entry``,
+    whose ``_table_bytes`` still sizes the table."""
     from . import _hip
 
     nb = int(getattr(_hip.lib(), entry + "_table_bytes")(len(jobs)))
     host, dev, ev = _take_table(nb + tail_bytes, device)
     if tail_bytes:
         fill_tail(host[nb:nb + tail_bytes], dev[nb:nb + tail_bytes])
-    _enqueue(entry, jobs, host, dev, host.numel())
+    if enqueue is not None:
+        enqueue(host, dev, host.numel())
+    else:
+        _enqueue(entry, jobs, host, dev, host.numel())
     ev.record()
     _tables.append((host, dev, ev))
     stream = torch.cuda.current_stream(device)
@@ -668,6 +673,19 @@ def tube_densify(jobs: Sequence, device) -> tuple:
     return _launch_fresh("td_tube_densify", jobs, device)
 
 
+def tube_densify_shots(jobs: Sequence, shots: Optional[Sequence], device) -> tuple:
+    """One td_tube_densify_shots launch, as ``tube_densify``; ``shots`` holds one ``_hip.DenseShots`` per job, or is None."""
+    from . import _hip
+
+    nb = int(_hip.lib().td_tube_densify_shots_table_bytes(len(jobs)))
+    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
+    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
+    arr = (_hip.DenseJob * len(jobs))(*jobs)
+    sarr = (_hip.DenseShots * len(jobs))(*shots) if shots is not None else None
+    _hip.check(_hip.lib().td_tube_densify_shots(arr, sarr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_tube_densify_shots")
+    return host, dev
+
+
 def _per_clip(v, n: int, name: str, multi: bool):
     """A scalar serves every clip; with a list of clips, a list or tuple gives one value each."""
     if multi and isinstance(v, (list, tuple)):
@@ -677,7 +695,7 @@ def _per_clip(v, n: int, name: str, multi: bool):
     return [v] * n
 
 
-def densify(boxes, T, row_frame=None, first=0, step=1, t0=0, span=None, heat=None, mode: str = "lerp", smooth=0):
+def densify(boxes, T, row_frame=None, first=0, step=1, t0=0, span=None, heat=None, mode: str = "lerp", smooth=0, shots=None, shots_t0=0):
     """Interpolate grounded tubes from the sampled frames to every decoded frame: ONE launch for one clip or for a list of
     clips (``boxes`` a list: ``row_frame``, ``span`` and ``heat`` are then lists too, or None, and ``T``, ``first``, ``step``,
     ``t0``, ``mode`` and ``smooth`` may be lists or one value for all).  Per clip:
@@ -688,7 +706,12 @@ def densify(boxes, T, row_frame=None, first=0, step=1, t0=0, span=None, heat=Non
       span       int64 (2,) or (K, 2) tube rows, as ``redact`` takes them; None: all rows;
       heat       uint8 (n_tube, mh, mw) from ``heat_from_attention``; None: no maps;
       mode       "hold" (what a frame_map does), "lerp" (straight lines between two rows) or "hull" (the cover of both rows: for ``redact``);
-      smooth     a radius in tube rows, 0..16: every row becomes the mean of the present rows around it first.
+      smooth     a radius in tube rows, 0..16: every row becomes the mean of the present rows around it first;
+      shots      what ``shot_cuts`` returned for the clip (a ``Shots``), or its int32 (n,) shot id per frame on the device, entry i
+                 for frame number ``shots_t0`` + i (a list of either, or of None, for a list of clips): the tube stops at the
+                 cuts (``td_tube_densify_shots``) - no box is interpolated, smoothed or covered across one, the row on the frame's
+                 own side of a cut stands alone.  Frames outside the array match every shot, so every chunk of a long video takes
+                 the whole video's array.  None: the call is what it was.
     The rule is exact - numpy float32 reproduces every bit - and stated in include/tubedetr_hip.h.  Returns ``DenseTubes`` (a
     list for a list), whose boxes, span and heat go to ``annotate`` / ``crop_tubes`` / ``redact`` with frame_map = None.  Nothing
     here synchronises or copies to the host, and bad arguments are refused before the device is touched."""
@@ -704,6 +727,12 @@ def densify(boxes, T, row_frame=None, first=0, step=1, t0=0, span=None, heat=Non
     else:
         frames_l, span_l, heat_l = [row_frame], [span], [heat]
     scalars = [_per_clip(v, n, k, multi) for v, k in ((T, "T"), (t0, "t0"), (first, "first"), (step, "step"), (mode, "mode"), (smooth, "smooth"))]
+    if shots is None:
+        shots_l = None
+    else:
+        shots_l = _as_list(shots, n, "shots") if multi else [shots]
+        shots_l = [sh.shot if isinstance(sh, Shots) else sh for sh in shots_l]
+        shots_t0_l = [_int_in("shots_t0", v, -MAX_FRAME_NO, MAX_FRAME_NO) for v in _per_clip(shots_t0, n, "shots_t0", multi)]
     if not torch.is_tensor(clips[0]) or not clips[0].is_cuda:
         # the scalars' refusals do not need a device: give them first, so that they are the same on a host without one
         for i in range(n):
@@ -735,6 +764,10 @@ def densify(boxes, T, row_frame=None, first=0, step=1, t0=0, span=None, heat=Non
             if len(f) != n_tube:
                 raise ValueError(f"row_frame has {len(f)} entries for {n_tube} tube rows")
             off, tail = tail, tail + (4 * n_tube + 15) // 16 * 16
+        if shots_l is not None and shots_l[i] is not None:
+            sh = shots_l[i] = _dev_tensor(shots_l[i], torch.int32, (), "shots", device)
+            if sh.dim() != 1 or sh.numel() > MAX_DENSE_T:
+                raise ValueError(f"shots: a Shots, or an int32 (n,) tensor of shot ids with n <= {MAX_DENSE_T}")
         prepared.append((b, f, s, h, off, n_tube, K, Ti, i))
     jobs, keep, results, uploads = [], [], [], []
     for b, f, s, h, off, n_tube, K, Ti, i in prepared:
@@ -751,7 +784,7 @@ def densify(boxes, T, row_frame=None, first=0, step=1, t0=0, span=None, heat=Non
         if off is not None:
             uploads.append((j, off, f))
         jobs.append(j)
-        keep.append((b, s, h, table))
+        keep.append((b, s, h, table, shots_l[i] if shots_l is not None else None))
         one = b.dim() == 2
         results.append(DenseTubes(dense.view(Ti, 4) if one else dense.view(Ti, K, 4), dspan.view(2) if one else dspan, valid.view(Ti) if one else valid.view(Ti, K),
                                   dheat.view(Ti, h.shape[1], h.shape[2]) if h is not None else None))
@@ -762,7 +795,183 @@ def densify(boxes, T, row_frame=None, first=0, step=1, t0=0, span=None, heat=Non
             j.row_frame = dev_tail.data_ptr() + off
         dev_tail.copy_(host_tail, non_blocking=True)
 
-    return _launch_pooled("td_tube_densify", jobs, keep, results, not multi, device, tail, fill_tail)
+    if shots_l is None:
+        return _launch_pooled("td_tube_densify", jobs, keep, results, not multi, device, tail, fill_tail)
+
+    def enqueue(host, dev, nbytes):
+        arr = (_hip.DenseJob * n)(*jobs)
+        sarr = (_hip.DenseShots * n)(*[_hip.DenseShots(_hip.ptr(sh), t, sh.numel() if sh is not None else 0) for sh, t in zip(shots_l, shots_t0_l)])
+        _hip.check(_hip.lib().td_tube_densify_shots(arr, sarr, n, host.data_ptr(), dev.data_ptr(), nbytes, _hip.stream_ptr()), "td_tube_densify_shots")
+
+    return _launch_pooled("td_tube_densify", jobs, keep, results, not multi, device, tail, fill_tail, enqueue)
+
+
+# ---- shot cuts in decoded frames (td_frame_stats, td_shot_cuts, csrc/frame_stats.hip) -----------------------------------------
+STAT_BINS = 64
+MAX_STAT_STEP = 8
+MAX_STAT_PIXELS = 1 << 24
+MAX_CUT_T = 1 << 20
+MAX_CUT_WINDOW = 16
+MAX_CUT_FRACTION = 1 << 20
+
+
+class FrameStats(NamedTuple):
+    """What ``frame_stats`` returns for one clip."""
+    hist: torch.Tensor  # int32 (T, 64) holding the uint32 counts: sampled pixels of frame t with luma >> 2 == b
+    sad: torch.Tensor   # int32 (T,) holding the uint32 sums: |luma_t - luma_(t-1)| over the sampled pixels; 0 for frame 0, and for a repeated frame
+    n: int              # sampled pixels per frame
+
+
+class Shots(NamedTuple):
+    """What ``shot_cuts`` returns for one clip; ``densify(..., shots=...)`` takes it."""
+    cut: torch.Tensor    # bool (T,): frame t is the first of a new shot
+    shot: torch.Tensor   # int32 (T,): the shot of frame t, counted from 0
+    count: torch.Tensor  # int32 (1,) on the device: the number of shots
+    d: torch.Tensor      # int32 (T,) holding uint32: the histogram distance to the frame before
+
+
+def sampled_pixels(sh: int, sw: int, step: int = 1) -> int:
+    """N of td_frame_stats: the pixels (y, x) with y % step == 0 and x % step == 0."""
+    return ((sh + step - 1) // step) * ((sw + step - 1) // step)
+
+
+def _stats_what(sh, sw, step):
+    step = _int_in("step", step, 1, MAX_STAT_STEP)
+    if sh * sw > MAX_STAT_PIXELS:
+        raise ValueError(f"frame size {sh} x {sw}: at most {MAX_STAT_PIXELS} pixels (the sum of differences is 32 bits wide)")
+    return step
+
+
+def stats_job(src: int, T: int, sh: int, sw: int, pix_fmt: str = "rgb24", step: int = 1, hist: Optional[int] = None, sad: Optional[int] = None,
+              src_planes: Optional[Sequence[int]] = None, src_pitches: Optional[Sequence[int]] = None, src_frame_stride: Optional[int] = None):
+    """One ``td_stats_job``: T frames of sh x sw in ``pix_fmt`` at device address ``src`` (planes, pitches and frame stride as in
+    ``overlay_job``), every ``step``-th pixel of every ``step``-th row; ``hist`` (uint32 [T][64]) and ``sad`` (uint32 [T]) are
+    device addresses, one of them may be None."""
+    from . import _hip
+
+    T, sh, sw = int(T), int(sh), int(sw)
+    _check_geometry(pix_fmt, T, sh, sw)
+    step = _stats_what(sh, sw, step)
+    if not hist and not sad:
+        raise ValueError("hist and sad are device addresses: at least one of them")
+    fmt, tight, sizes = _planes(pix_fmt, sh, sw)
+    j = _hip.StatsJob()
+    (j.src0, j.src1, j.src2), (j.src_pitch0, j.src_pitch1, j.src_pitch2), j.src_frame_stride = _describe(src, sizes, tight, src_planes, src_pitches, src_frame_stride)
+    j.fmt, j.T, j.sh, j.sw, j.step = fmt, T, sh, sw, step
+    j.hist, j.sad = hist, sad
+    return j
+
+
+def _fraction(name: str, v) -> Tuple[int, int]:
+    try:
+        num, den = v
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} {v!r}: two integers (numerator, denominator)") from None
+    return _int_in(name + " numerator", num, 0, MAX_CUT_FRACTION), _int_in(name + " denominator", den, 1, MAX_CUT_FRACTION)
+
+
+def _cuts_what(hist, sad, peak, window):
+    return _fraction("hist", hist) + _fraction("sad", sad) + _fraction("peak", peak) + (_int_in("window", window, 0, MAX_CUT_WINDOW),)
+
+
+def cuts_job(hist: int, sad: int, T: int, n: int, cut: int, shot: int, n_shots: int, d: Optional[int] = None, hist_thr=(1, 4), sad_thr=(8, 1), peak=(3, 1),
+             window: int = 4):
+    """One ``td_cuts_job``: the statistics ``hist`` (uint32 [T][64]) and ``sad`` (uint32 [T]) of T frames of ``n`` sampled pixels
+    decided into ``cut`` (bytes [T]), ``shot`` (int32 [T]), ``n_shots`` (int32 [1]) and, optionally, ``d`` (uint32 [T]): device
+    addresses.  The thresholds are (numerator, denominator) pairs, ``window`` the peak test's radius in frames."""
+    from . import _hip
+
+    T, n = _int_in("T", T, 0, MAX_CUT_T), _int_in("n", n, 1, MAX_STAT_PIXELS)
+    what = _cuts_what(hist_thr, sad_thr, peak, window)
+    if not (hist and sad and cut and shot and n_shots):
+        raise ValueError("hist, sad, cut, shot and n_shots are device addresses, not None")
+    j = _hip.CutsJob()
+    j.hist, j.sad, j.T, j.N = hist, sad, T, n
+    j.hist_num, j.hist_den, j.sad_num, j.sad_den, j.peak_num, j.peak_den, j.w = what
+    j.d, j.cut, j.shot, j.n_shots = d, cut, shot, n_shots
+    return j
+
+
+def launch_frame_stats(jobs: Sequence, device) -> tuple:
+    """One td_frame_stats launch on the current stream with freshly allocated job tables; returns them: the caller keeps them
+    alive until the stream has passed the launch (``frame_stats`` recycles its own instead)."""
+    return _launch_fresh("td_frame_stats", jobs, device)
+
+
+def launch_shot_cuts(jobs: Sequence, device) -> tuple:
+    """One td_shot_cuts launch, as ``launch_frame_stats``."""
+    return _launch_fresh("td_shot_cuts", jobs, device)
+
+
+def frame_stats(frames: Union[DeviceFrames, Sequence[DeviceFrames]], step: int = 1):
+    """A luma histogram per frame and the sum of absolute luma differences to the frame before, read from the decoded planes in
+    ONE launch for one clip or for a list of clips (mixed sizes and formats).  ``step`` in 1..8 takes every ``step``-th pixel of
+    every ``step``-th row, and the bytes read fall with it.  The rule is integers and stated in include/tubedetr_hip.h; a long
+    video done in chunks overlaps them by one frame.  Returns ``FrameStats`` (a list for a list).  Nothing here synchronises or
+    copies to the host, and bad arguments are refused before the device is touched."""
+    single = isinstance(frames, DeviceFrames)
+    clips = [frames] if single else list(frames)
+    if len(clips) == 0:
+        return []
+    if not isinstance(clips[0], DeviceFrames):
+        raise ValueError("frames: DeviceFrames on one device")
+    device = clips[0].data.device
+    for c in clips:  # every refusal comes before the first allocation and the launch
+        if not isinstance(c, DeviceFrames) or c.data.device != device:
+            raise ValueError("frames: DeviceFrames on one device")
+        _stats_what(c.h, c.w, step)
+    jobs, keep, results = [], [], []
+    for c in clips:
+        out = torch.empty(max(c.T, 1) * (STAT_BINS + 1), dtype=torch.int32, device=device)  # (T = 0 still has an address)
+        hist, sad = out[:c.T * STAT_BINS], out[c.T * STAT_BINS:c.T * (STAT_BINS + 1)]
+        if c.T > 0:  # (a clip without frames has no bytes, and its tensor no address: it is no job)
+            jobs.append(stats_job(c.data.data_ptr(), c.T, c.h, c.w, c.pix_fmt, step, out.data_ptr(), out.data_ptr() + 4 * c.T * STAT_BINS))
+            keep.append((c.data,))
+        results.append(FrameStats(hist.view(c.T, STAT_BINS), sad, sampled_pixels(c.h, c.w, step)))
+    if not jobs:
+        return results[0] if single else results
+    return _launch_pooled("td_frame_stats", jobs, keep, results, single, device)
+
+
+def shot_cuts(frames_or_stats, step: int = 1, hist=(1, 4), sad=(8, 1), peak=(3, 1), window: int = 4):
+    """Where the hard cuts of decoded clips are: ``frames_or_stats`` is a ``DeviceFrames`` (``frame_stats`` with ``step`` runs
+    first), a ``FrameStats``, or a list of either kind.  Frame t starts a new shot when its histogram distance d[t] to the frame
+    before exceeds ``hist`` = (num, den) of its maximum 2 n, its sum of differences exceeds ``sad`` = (num, den) grey levels per
+    sampled pixel, and d[t] is the first largest value within ``window`` frames and more than ``peak`` = (num, den) times the
+    mean of the others there - the rule, in integers, is stated in include/tubedetr_hip.h.  A one-frame flash gives one cut, at
+    its first frame; fades and wipes give none.  The defaults are starting values tried on synthetic clips only: no footage has
+    validated them.  Returns ``Shots`` (a list for a list); nothing synchronises, ``Shots.count`` stays on the device."""
+    single = isinstance(frames_or_stats, (DeviceFrames, FrameStats))
+    items = [frames_or_stats] if single else list(frames_or_stats)
+    if len(items) == 0:
+        return []
+    _cuts_what(hist, sad, peak, window)
+    if all(isinstance(v, DeviceFrames) for v in items):
+        _int_in("step", step, 1, MAX_STAT_STEP)
+        items = frame_stats(items, step)
+    prepared = []
+    for v in items:  # every refusal comes before the first allocation and the launch
+        if not isinstance(v, FrameStats):
+            raise ValueError("frames_or_stats: DeviceFrames or FrameStats, one kind per call")
+        h, s = v.hist, v.sad
+        if not (torch.is_tensor(h) and torch.is_tensor(s) and h.is_cuda and s.device == h.device and h.dtype == torch.int32 and s.dtype == torch.int32
+                and h.dim() == 2 and h.shape[1] == STAT_BINS and s.dim() == 1 and s.shape[0] == h.shape[0]):
+            raise ValueError(f"FrameStats: hist int32 (T, {STAT_BINS}) and sad int32 (T,) on the device")
+        if h.device != items[0].hist.device:
+            raise ValueError("frames_or_stats: statistics on one device")
+        prepared.append((h.contiguous(), s.contiguous(), _int_in("T", h.shape[0], 0, MAX_CUT_T), _int_in("FrameStats.n", v.n, 1, MAX_STAT_PIXELS)))
+    device = prepared[0][0].device
+    jobs, keep, results = [], [], []
+    for h, s, T, n in prepared:
+        words = torch.empty(2 * max(T, 1) + 1, dtype=torch.int32, device=device)
+        flags = torch.empty(max(T, 1), dtype=torch.bool, device=device)
+        d, shot, count = words[:T], words[max(T, 1):max(T, 1) + T], words[2 * max(T, 1):]
+        # (a tensor without elements has no address: T = 0 still hands addresses over, and none of them is read or written but n_shots)
+        jobs.append(cuts_job(h.data_ptr() or words.data_ptr(), s.data_ptr() or words.data_ptr(), T, n, flags.data_ptr(), words.data_ptr() + 4 * max(T, 1),
+                             words.data_ptr() + 8 * max(T, 1), words.data_ptr(), hist, sad, peak, window))
+        keep.append((h, s))
+        results.append(Shots(flags[:T], shot, count, d))
+    return _launch_pooled("td_shot_cuts", jobs, keep, results, single, device)
 
 
 # ---- K labelled tubes and a moment timeline in one pass (td_tube_overlay_multi, csrc/overlay_multi.hip) -----------------------
