@@ -1249,6 +1249,76 @@ typedef struct td_dense_shots {
 size_t td_tube_densify_shots_table_bytes(int n_jobs);
 int td_tube_densify_shots(const td_dense_job* jobs, const td_dense_shots* shots, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
 
+/* ---- Boxes that follow the object's pixels between sampled frames (an addition WITHIN ABI 11: nothing above changed) -----
+ * td_tube_densify fills the decoded frames between two sampled ones by arithmetic on the boxes alone; an object does not move
+ * on a straight line between two samples.  td_tube_follow is the stage between td_tube_densify and td_tube_overlay /
+ * td_tube_crop / td_tube_redact: it looks at the pixels and moves every in-between box onto the object by block matching
+ * against the nearest sampled frame.  Per job (one clip):
+ *   src0..2, src_pitch0..2, src_frame_stride, fmt, T, sh, sw: the source side of td_overlay_job, word for word (every plane of
+ *     the format is described and checked, although the chroma planes are never read);
+ *   K in 1..8;
+ *   boxes   fp32 [T][K][4], xyxy in source pixels, one box per decoded frame and tube: what td_tube_densify writes (four NaNs:
+ *           absent);
+ *   anchor  bytes [T]: non-zero - the boxes of this frame are the model's own (a sampled frame);
+ *   shot    int32 [T], nullable: td_shot_cuts' `shot` for these same T frames;
+ *   radius  R in 0..16; reach in 1..64; accept_num in 0..2^20, accept_den in 1..2^20;
+ *   outputs, device pointers: out fp32 [T][K][4] (required); offset int32 [T][K][2] as (dy, dx), cost uint32 [T][K] and status
+ *           bytes [T][K], each nullable.  out may BE boxes: a unit (t, k) reads only its own box and anchor boxes, writes only
+ *           its own, and an anchor box is never changed (it is written back with its own bits).
+ * The luma L of pixel (y, x) is td_frame_stats': I420 and NV12: the Y byte as stored; RGB24: (77 R + 150 G + 29 B + 128) >> 8.
+ * The rule for frame t and tube k, B = boxes[t][k] (this comment is the specification; all integers except step 8):
+ *   1. COPIED (status 0) when anchor[t] != 0 or a coordinate of B is not finite: out gets B's bit patterns, offset (0, 0),
+ *      cost 0, status 0.  Every later "copied" means the same.
+ *   2. The anchor frame g: for d = 1 .. reach in this order, q = t - d and then q = t + d; the first q qualifies with
+ *      0 <= q < T, anchor[q] != 0, every coordinate of boxes[q][k] finite and, with shot given, shot[q] == shot[t].  The nearer
+ *      anchor wins, of two equally near the earlier.  None qualifies: copied.
+ *   3. Rounding is td_tube_overlay's (finite values clamped to +-2^20, then (int)floorf(v + 0.5f) in fp32), applied to the anchor
+ *      box, (ax0, ay0, ax1, ay1), and to B, (bx0, by0, bx1, by1).
+ *   4. The template: x0 = max(ax0, 0), y0 = max(ay0, 0), x1 = min(ax1, sw), y1 = min(ay1, sh); w = x1 - x0, h = y1 - y0; w <= 0
+ *      or h <= 0: copied.  The 16 x 16 sample points are px[j] = x0 + ((2 j + 1) w) / 32 and py[i] = y0 + ((2 i + 1) h) / 32
+ *      (integer divisions; always inside the clamped box), and tem[i][j] = L of frame g at (py[i], px[j]).
+ *   5. The predicted shift: ddx = ((bx0 + bx1) - (ax0 + ax1)) >> 1, ddy alike from the y's, on the UNCLAMPED rounded corners;
+ *      >> is the arithmetic shift, which floors.
+ *   6. The candidates are (dy, dx) with -R <= dy, dx <= R, and
+ *      c(dy, dx) = sum_{i,j} | L_t(clamp(py[i] + ddy + dy, 0, sh - 1), clamp(px[j] + ddx + dx, 0, sw - 1)) - tem[i][j] |,
+ *      at most 65 280.  Clamping to the frame's edge keeps every candidate defined.
+ *   7. The best candidate has the smallest c; ties go to the smallest dy^2 + dx^2, then the smallest dy, then the smallest dx
+ *      (so a flat picture answers (0, 0)).  cost = that c.
+ *   8. ACCEPTED (status 1) iff c * accept_den <= accept_num * 256 in 64-bit integers (accept_num / accept_den grey levels per
+ *      sample): offset = (dy, dx) and out = (B.x0 + (float)dx, B.y0 + (float)dy, B.x1 + (float)dx, B.y1 + (float)dy), each ONE
+ *      fp32 addition; with dy = dx = 0 B's bits are copied.  REJECTED (status 2) otherwise: out gets B's bits, offset (0, 0),
+ *      and cost keeps c.
+ * Translation only: the template keeps the anchor's scale.  Every frame is matched against an anchor, never against its
+ * neighbour: nothing drifts, and every (t, k) is independent of every other.  A long video done in chunks overlaps them by
+ * `reach` frames.  A rejected match (an occlusion, the object leaving the frame) leaves the interpolated box.  The Python
+ * layer's default for accept (24 / 1) is a starting value: nobody has tried it on real footage.
+ * Refused on the host with a message that names the field (nothing is launched): every violation of a plane (null, pitch
+ * below the row, frame stride below the plane) in td_tube_overlay's words; an unknown fmt; T < 0; sh, sw outside 1..16384; K,
+ * radius, reach, accept_num or accept_den outside its range; boxes, anchor or out NULL.  T = 0 is legal and writes nothing.
+ * One launch serves any number of jobs of mixed formats, sizes, K and radius.  Job table: as for td_tube_overlay,
+ * td_tube_follow_table_bytes(n_jobs) bytes.  No allocation, no synchronisation, no atomics; the same call returns the same bits. */
+typedef struct td_follow_job {
+  const void* src0; /* rgb24 pixels, or Y */
+  const void* src1; /* I420: U; NV12: UV pairs; RGB24: ignored */
+  const void* src2; /* I420: V; else ignored */
+  long long src_frame_stride;
+  int src_pitch0, src_pitch1, src_pitch2;
+  int fmt;
+  int T, sh, sw;
+  int K;
+  const float* boxes;
+  const unsigned char* anchor;
+  const int* shot;
+  int radius, reach;
+  int accept_num, accept_den;
+  float* out;
+  int* offset;
+  unsigned* cost;
+  unsigned char* status;
+} td_follow_job;
+size_t td_tube_follow_table_bytes(int n_jobs);
+int td_tube_follow(const td_follow_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

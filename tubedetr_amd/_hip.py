@@ -162,6 +162,13 @@ class CutsJob(C.Structure):
                [(n, C.c_void_p) for n in ("d", "cut", "shot", "n_shots")]
 
 
+class FollowJob(C.Structure):
+    """td_follow_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("src0", "src1", "src2")] + [("src_frame_stride", C.c_longlong)] + [(n, C.c_int) for n in ("src_pitch0", "src_pitch1", "src_pitch2")] + \
+               [(n, C.c_int) for n in ("fmt", "T", "sh", "sw", "K")] + [(n, C.c_void_p) for n in ("boxes", "anchor", "shot")] + \
+               [(n, C.c_int) for n in ("radius", "reach", "accept_num", "accept_den")] + [(n, C.c_void_p) for n in ("out", "offset", "cost", "status")]
+
+
 class ReplicaMapsOut(C.Structure):
     """td_replica_maps_out."""
     _fields_ = [(n, C.c_void_p) for n in ("owner", "vid_of_frame", "vid_of_clip", "query_mask", "frame_dest", "clip_of", "vis_src", "vis_dst", "txt_src", "txt_dst",
@@ -252,6 +259,7 @@ _SIGS = {
     "td_frame_stats": [C.POINTER(StatsJob), _I, _P, _P, _SZ, _P],
     "td_shot_cuts": [C.POINTER(CutsJob), _I, _P, _P, _SZ, _P],
     "td_tube_densify_shots": [C.POINTER(DenseJob), C.POINTER(DenseShots), _I, _P, _P, _SZ, _P],
+    "td_tube_follow": [C.POINTER(FollowJob), _I, _P, _P, _SZ, _P],
     "td_conv_gemm_route": [C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_linear_ex_route": [C.POINTER(LinearExDesc), _I, C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_conv_wgrad_batch_plan": [C.POINTER(WgradJob), _I, _I, _I, _I, C.POINTER(WgradPlanJob), C.POINTER(WgradPlanLaunch), C.POINTER(C.c_int)],
@@ -272,6 +280,7 @@ _SIZE_SIGS = {
     "td_frame_stats_table_bytes": [_I],
     "td_shot_cuts_table_bytes": [_I],
     "td_tube_densify_shots_table_bytes": [_I],
+    "td_tube_follow_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
