@@ -1319,6 +1319,80 @@ typedef struct td_follow_job {
 size_t td_tube_follow_table_bytes(int n_jobs);
 int td_tube_follow(const td_follow_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
 
+/* ---- Rendered frames exported: cut, downscaled, converted (an addition WITHIN ABI 11: nothing above changed) --------------
+ * The last stage of the render chain: the frames that td_tube_overlay / td_tube_redact wrote become what an encoder or a browser
+ * takes - only the frames of the answer, smaller, in another pixel format, padded to even sides (the reference's demo decodes
+ * to rgb24 and writes yuv420p with pad=ceil(iw/2)*2:ceil(ih/2)*2: demo_stvg.py:95,193).  One pass, and it decides how many
+ * bytes cross to the host.  Per job (this comment is the specification; everything is exact integers):
+ *   Source: T frames of sh x sw in src_fmt = TD_SRC_RGB24 / TD_SRC_I420 / TD_SRC_NV12; src0..2, src_pitch0..2 and
+ *     src_frame_stride as in td_overlay_job (odd sizes are legal, chroma planes are (sh + 1) / 2 x (sw + 1) / 2).
+ *   Colour: matrix and full_range describe whichever side is yuv; with both sides yuv they describe both, so a yuv -> yuv job
+ *     never changes matrix or range.  An rgb24 -> rgb24 job ignores them.
+ *   Frames: To output frames.  take = NULL: To must equal T and output frame i is source frame i.  Else take is a device int32
+ *     [To] and output frame i is source frame take[i]; an entry outside [0, T) makes output frame i a BLANK frame.  valid, device
+ *     bytes [To], nullable: 1 for a taken frame, 0 for a blank one.
+ *   Picture: oh x ow with 1 <= oh <= sh and 1 <= ow <= sw - the same size or smaller; nothing is enlarged.
+ *   Destination: dst_fmt, dst0..2, dst_pitch0..2, dst_frame_stride describe To frames of dh x dw with dh >= oh, dw >= ow (chroma
+ *     planes (dh + 1) / 2 x (dw + 1) / 2).  The picture sits at the top left; every other sample of a frame, and every sample of
+ *     a blank frame, is pad: three bytes in the DESTINATION's colour space (R, G, B; or luma pad[0], U pad[1], V pad[2]).  A
+ *     chroma sample (cy, cx) with cy < (oh + 1) / 2 and cx < (ow + 1) / 2 belongs to the picture, the others are pad.  The
+ *     destination must not overlap the source: there is no export in place.
+ * The rule is a composition of three stages.
+ *   A. Area resize of a plane of n_y x n_x samples to m_y x m_x (m <= n), per channel.  Along one axis output sample j takes
+ *      source sample i with weight w(j, i) = max(0, min((j + 1) n, (i + 1) m) - max(j n, i m)); the weights of one j sum to n.
+ *      With D = n_y n_x and S = sum over y and x of wy wx v, the value is (S + (D >> 1)) / D (integer division).  Equal sizes
+ *      give an exact copy; an exact 2:1 gives the rounded 2 x 2 mean (S' + 2) >> 2.
+ *   B. yuv -> rgb of a pixel: td_clip_resample_src's rule, unchanged - chroma sample (y >> 1, x >> 1) and the 16-bit
+ *      coefficient table above.
+ *   C. rgb -> yuv of a picture of h x w pixels.  Luma of pixel (y, x): td_tube_overlay's colour rule (color_in_space),
+ *      Y = clamp((yr R + yg G + yb B + 2^20 yo + 2^19) >> 20) with the round(2^20 x) coefficients given there.  Chroma sample
+ *      (cy, cx) covers the n = 1, 2 or 4 pixels of its 2 x 2 block that exist (an odd last row or column has fewer: centre
+ *      siting); with Rs, Gs, Bs their sums, U = clamp((ur Rs + ug Gs + ub Bs + n (2^20 128 + 2^19)) >> (20 + log2 n)), V alike
+ *      (>> = floor division, clamp to [0, 255]).  Every accumulator lies in [0, 2^30]; a solid colour gives exactly
+ *      color_in_space(colour); the result is within 0.5004 of a level of the float64 formula applied to the block's mean.
+ * By format pair:
+ *   rgb24 -> rgb24   A on the three channels (sh x sw -> oh x ow);
+ *   yuv -> yuv       (I420 / NV12 in any combination) A on the Y plane (sh x sw -> oh x ow) and on the U and the V plane
+ *                    independently ((sh + 1) / 2 x (sw + 1) / 2 -> (oh + 1) / 2 x (ow + 1) / 2); I420 <-> NV12 is only packing,
+ *                    and at equal size the job repacks byte for byte;
+ *   rgb24 -> yuv     A, rounded to bytes, then C on the oh x ow picture;
+ *   yuv -> rgb24     B on every source pixel, then A.
+ * Limits: sh 1..16384; sw 1..8192; dh, dw 1..16384; T >= 0, To >= 0 (To = 0 writes nothing; T = 0 makes every taken frame
+ * blank).  A job that resizes (oh != sh or ow != sw) needs sh sw <= 2^24, so that S + (D >> 1) <= 255.5 x 2^24 < 2^32 fits
+ * unsigned 32 bits; a same-size job has no such bound.  LDS: a workgroup stages, per source row, the columns under 256
+ * output columns, and needs 9216 + 3 min(sw, ceil(256 sw / ow) + 1) + 24 <= 65536 bytes (rgb24; a yuv source needs less) - an
+ * inequality that every sw <= 8192 satisfies, so the bound on sw is the only one: every resizing job with ow <= 4096 and every
+ * same-size job up to sw = 8192 is admitted.  A violation returns an error whose message names the field (ow / oh for an
+ * enlargement, "sh * sw", dh / dw, To, the plane fields in td_tube_overlay's words, "overlaps"); nothing is launched.
+ * No byte outside the job's destination rows of its To frames and of valid is written (not the row padding between the row and
+ * the pitch); no byte outside the source rows of the taken frames is read.  One launch serves any number of jobs of mixed
+ * formats and sizes.  Job table: as for td_tube_overlay, td_frame_export_table_bytes(n_jobs) bytes.  No allocation, no
+ * synchronisation, no atomics; the same call returns the same bits. */
+typedef struct td_export_job {
+  const void* src0; /* rgb24 pixels, or Y */
+  const void* src1; /* I420: U; NV12: UV pairs; RGB24: ignored */
+  const void* src2; /* I420: V; else ignored */
+  long long src_frame_stride;
+  int src_pitch0, src_pitch1, src_pitch2;
+  int src_fmt;
+  int matrix, full_range;
+  int T, sh, sw;
+  const int* take;
+  int To;
+  int oh, ow;
+  void* dst0;
+  void* dst1;
+  void* dst2;
+  long long dst_frame_stride;
+  int dst_pitch0, dst_pitch1, dst_pitch2;
+  int dst_fmt;
+  int dh, dw;
+  unsigned char pad[3];
+  unsigned char* valid;
+} td_export_job;
+size_t td_frame_export_table_bytes(int n_jobs);
+int td_frame_export(const td_export_job* jobs, int n_jobs, void* table_host, void* table_dev, size_t table_bytes, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,14 @@ class FollowJob(C.Structure):
                [(n, C.c_int) for n in ("radius", "reach", "accept_num", "accept_den")] + [(n, C.c_void_p) for n in ("out", "offset", "cost", "status")]
 
 
+class ExportJob(C.Structure):
+    """td_export_job."""
+    _fields_ = [(n, C.c_void_p) for n in ("src0", "src1", "src2")] + [("src_frame_stride", C.c_longlong)] + \
+               [(n, C.c_int) for n in ("src_pitch0", "src_pitch1", "src_pitch2", "src_fmt", "matrix", "full_range", "T", "sh", "sw")] + [("take", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("To", "oh", "ow")] + [(n, C.c_void_p) for n in ("dst0", "dst1", "dst2")] + [("dst_frame_stride", C.c_longlong)] + \
+               [(n, C.c_int) for n in ("dst_pitch0", "dst_pitch1", "dst_pitch2", "dst_fmt", "dh", "dw")] + [("pad", C.c_ubyte * 3), ("valid", C.c_void_p)]
+
+
 class ReplicaMapsOut(C.Structure):
     """td_replica_maps_out."""
     _fields_ = [(n, C.c_void_p) for n in ("owner", "vid_of_frame", "vid_of_clip", "query_mask", "frame_dest", "clip_of", "vis_src", "vis_dst", "txt_src", "txt_dst",
@@ -260,6 +268,7 @@ _SIGS = {
     "td_shot_cuts": [C.POINTER(CutsJob), _I, _P, _P, _SZ, _P],
     "td_tube_densify_shots": [C.POINTER(DenseJob), C.POINTER(DenseShots), _I, _P, _P, _SZ, _P],
     "td_tube_follow": [C.POINTER(FollowJob), _I, _P, _P, _SZ, _P],
+    "td_frame_export": [C.POINTER(ExportJob), _I, _P, _P, _SZ, _P],
     "td_conv_gemm_route": [C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_linear_ex_route": [C.POINTER(LinearExDesc), _I, C.POINTER(Epilogue), _I, _I, C.POINTER(GemmRoute), C.POINTER(C.c_int)],
     "td_conv_wgrad_batch_plan": [C.POINTER(WgradJob), _I, _I, _I, _I, C.POINTER(WgradPlanJob), C.POINTER(WgradPlanLaunch), C.POINTER(C.c_int)],
@@ -281,6 +290,7 @@ _SIZE_SIGS = {
     "td_shot_cuts_table_bytes": [_I],
     "td_tube_densify_shots_table_bytes": [_I],
     "td_tube_follow_table_bytes": [_I],
+    "td_frame_export_table_bytes": [_I],
     "td_resnet_bwd_table_bytes": [C.POINTER(C.c_int), _I],
     "td_resnet_fwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],
     "td_resnet_bwd_ws_bytes": [_I, _I, _I, C.POINTER(C.c_int), _I, _I],

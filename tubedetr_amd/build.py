@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtubedetr_hip.so")
-SOURCES = ["api.cpp", "gemm_conv.hip", "conv_wgrad.hip", "prep.hip", "elementwise.hip", "attention.hip", "resnet_exec.hip", "optim.hip", "criterion.hip", "stem.hip", "bottleneck.hip", "cross_attn.hip", "chain.hip", "augment.hip", "replica_maps.hip", "overlay.hip", "overlay_multi.hip", "moments.hip", "tube_crop.hip", "redact.hip", "tube_dense.hip", "frame_stats.hip", "tube_follow.hip"]
+SOURCES = ["api.cpp", "gemm_conv.hip", "conv_wgrad.hip", "prep.hip", "elementwise.hip", "attention.hip", "resnet_exec.hip", "optim.hip", "criterion.hip", "stem.hip", "bottleneck.hip", "cross_attn.hip", "chain.hip", "augment.hip", "replica_maps.hip", "overlay.hip", "overlay_multi.hip", "moments.hip", "tube_crop.hip", "redact.hip", "tube_dense.hip", "frame_stats.hip", "tube_follow.hip", "frame_export.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
 
 

@@ -1,6 +1,6 @@
 // What the "job table" kernels on decoded frames share: td_clip_resample / td_clip_resample_src (augment.hip), td_tube_overlay
-// (overlay.hip), td_tube_overlay_multi (overlay_multi.hip), td_tube_crop (tube_crop.hip), td_tube_redact (redact.hip) and td_tube_densify (tube_dense.hip), the stage in front
-// of the last three.  One launch serves a table of job records; a
+// (overlay.hip), td_tube_overlay_multi (overlay_multi.hip), td_tube_crop (tube_crop.hip), td_tube_redact (redact.hip), td_tube_densify (tube_dense.hip), the stage in front
+// of the last three, and td_frame_export (frame_export.hip), the stage behind them all.  One launch serves a table of job records; a
 // workgroup finds its job by block_begin.  include/tubedetr_hip.h defines the crop's and the redaction's rectangles by reference
 // to the overlay's ("rounding is td_tube_overlay's", "the margin is td_tube_crop's step 4"): each step of that rule exists once,
 // here, and the three kernels compose the steps.  The host half is the plane geometry of a pixel format, the checks of a job's
