@@ -16,6 +16,9 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
+from . import _hip
+from .frame_jobs import _MATRICES, _PIX_FMTS, _describe, _frame_bytes, _planes, _put_planes, clip_resample, clip_resample_src  # noqa: F401  (the launchers are part of this module's interface)
+
 # resolution -> (scales, max_size, resizes, crop, test_size)  (datasets/video_transforms.py:339-405)
 _TABLE = {
     128: ([96, 128], 213, [80, 100, 120], 64, [128]),
@@ -178,8 +181,6 @@ def resample_job(src: int, T: int, sh: int, sw: int, flip: bool, stage: Resample
                  mask: Optional[int] = None, src_pitch: Optional[int] = None, src_frame_stride: Optional[int] = None):
     """One ``td_resample_job``: T packed rgb24 frames of sh x sw at device address ``src`` through ``stage`` into ``dst``
     (interleaved (T, wh, ww, 3), or planar frames frame_off.. of a padded (n, 3, H, W) video with its (n, H, W) mask)."""
-    from . import _hip
-
     pitch = 3 * sw if src_pitch is None else src_pitch
     j = _hip.ResampleJob()
     j.src, j.src_frame_stride, j.src_pitch = src, (pitch * sh if src_frame_stride is None else src_frame_stride), pitch
@@ -187,10 +188,6 @@ def resample_job(src: int, T: int, sh: int, sw: int, flip: bool, stage: Resample
     j.rh, j.rw, j.wy, j.wx, j.wh, j.ww = stage.rh, stage.rw, stage.wy, stage.wx, stage.wh, stage.ww
     j.dst, j.planar, j.frame_off, j.H, j.W, j.mask = dst, int(bool(planar)), frame_off, H, W, mask
     return j
-
-
-_PIX_FMTS = ("rgb24", "yuv420p", "nv12")
-_MATRICES = ("bt601", "bt709")
 
 
 @dataclass
@@ -227,10 +224,7 @@ class DecodedClip:
 
     @property
     def nbytes_per_frame(self) -> int:
-        if self.pix_fmt == "rgb24":
-            return 3 * self.w * self.h
-        ch, cw = self.chroma_hw
-        return self.w * self.h + 2 * cw * ch
+        return _frame_bytes(self.pix_fmt, self.h, self.w)
 
     @property
     def nbytes(self) -> int:
@@ -243,56 +237,11 @@ def resample_src_job(src: int, T: int, sh: int, sw: int, flip: bool, stage: Resa
     """One ``td_resample_src_job``: ``resample_job`` for T frames in ``pix_fmt`` at device address ``src``.  Without
     ``planes`` / ``pitches`` / ``frame_stride`` the frames are tightly packed (``DecodedClip``); else ``planes`` are the
     device addresses of frame 0's planes (``src`` is ignored) and ``pitches`` their row pitches."""
-    from . import _hip
-
-    ch, cw = (sh + 1) // 2, (sw + 1) // 2
-    if pix_fmt == "rgb24":
-        fmt, tight, sizes = _hip.TD_SRC_RGB24, [3 * sw], [3 * sw * sh]
-    elif pix_fmt == "yuv420p":
-        fmt, tight, sizes = _hip.TD_SRC_I420, [sw, cw, cw], [sw * sh, cw * ch, cw * ch]
-    elif pix_fmt == "nv12":
-        fmt, tight, sizes = _hip.TD_SRC_NV12, [sw, 2 * cw], [sw * sh, 2 * cw * ch]
-    else:
-        raise ValueError(f"pix_fmt {pix_fmt!r}: one of {_PIX_FMTS}")
-    pitches = list(tight if pitches is None else pitches)
-    if planes is None:
-        planes = [src + sum(sizes[:i]) for i in range(len(sizes))]
-        if frame_stride is None:
-            frame_stride = sum(sizes)
-    assert len(planes) == len(pitches) == len(sizes) and frame_stride is not None, "one address and one pitch per plane, and the frame stride"
-    planes, pitches = list(planes) + [None] * (3 - len(sizes)), pitches + [0] * (3 - len(sizes))
+    fmt, tight, sizes = _planes(pix_fmt, sh, sw)
     j = _hip.ResampleSrcJob()
-    j.plane0, j.plane1, j.plane2 = planes
-    j.pitch0, j.pitch1, j.pitch2 = pitches
-    j.frame_stride, j.fmt, j.matrix, j.full_range = frame_stride, fmt, _MATRICES.index(matrix), int(bool(full_range))
+    _put_planes(j, "", _describe(src, sizes, tight, planes, pitches, frame_stride))
+    j.fmt, j.matrix, j.full_range = fmt, _MATRICES.index(matrix), int(bool(full_range))
     j.T, j.sh, j.sw, j.flip = T, sh, sw, int(bool(flip))
     j.rh, j.rw, j.wy, j.wx, j.wh, j.ww = stage.rh, stage.rw, stage.wy, stage.wx, stage.wh, stage.ww
     j.dst, j.planar, j.frame_off, j.H, j.W, j.mask = dst, int(bool(planar)), frame_off, H, W, mask
     return j
-
-
-def clip_resample_src(jobs: Sequence, device) -> tuple:
-    """``clip_resample`` for ``resample_src_job`` jobs (td_clip_resample_src)."""
-    from . import _hip
-
-    lib = _hip.lib()
-    nb = int(lib.td_clip_resample_src_table_bytes(len(jobs)))
-    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
-    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
-    arr = (_hip.ResampleSrcJob * len(jobs))(*jobs)
-    _hip.check(lib.td_clip_resample_src(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_clip_resample_src")
-    return host, dev
-
-
-def clip_resample(jobs: Sequence, device) -> tuple:
-    """One td_clip_resample launch on the current stream with freshly allocated job tables; returns them: the caller keeps
-    them alive until the stream has passed the launch (``ClipPipeline.stage_raw`` recycles its own instead)."""
-    from . import _hip
-
-    lib = _hip.lib()
-    nb = int(lib.td_clip_resample_table_bytes(len(jobs)))
-    host = torch.empty(max(nb, 256), dtype=torch.uint8, pin_memory=True)
-    dev = torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
-    arr = (_hip.ResampleJob * len(jobs))(*jobs)
-    _hip.check(lib.td_clip_resample(arr, len(jobs), host.data_ptr(), dev.data_ptr(), nb, _hip.stream_ptr()), "td_clip_resample")
-    return host, dev

@@ -11,11 +11,12 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import torch
 from torch import nn
 
+from .. import _hip
+from ..frame_jobs import release_table, take_table
+
 
 def sted_decode(steds: torch.Tensor) -> torch.Tensor:
     """steds [n, T, 2] logits (-inf = impossible position) -> int64 [n, 2] (start index, end index), end > start."""
-    from .. import _hip
-
     steds = steds.float().contiguous()
     n, T, _ = steds.shape
     out = torch.empty((n, 2), dtype=torch.int64, device=steds.device)
@@ -82,25 +83,19 @@ class Moments(NamedTuple):
     count: torch.Tensor   # int32 [n_videos]
 
 
-# host tables (window table, frame ids) go up through render's pool of (pinned, device, event) triples: the event is recorded
-# behind the last launch that reads the device side, and a triple is taken again only once it has completed (a query, never a wait).
+# host tables (window table, frame ids) go up through the frame jobs' pool of (pinned, device, event) triples (frame_jobs.py): the event
+# is recorded behind the last launch that reads the device side, and a triple is taken again only once it has completed (a query, never a wait).
 def _upload(values: torch.Tensor, device):
-    """Host tensor -> (device copy, triple); the caller records triple[2] behind its last reader and hands the triple to _release."""
-    from ..render import _take_table
-
+    """Host tensor -> (device copy, triple); the caller hands the triple to _release behind the device copy's last reader."""
     nb = values.numel() * values.element_size()
-    triple = _take_table(nb, device)
+    triple = take_table(nb, device)
     host, dev, _ = triple
     host[:nb].copy_(values.contiguous().view(-1).view(torch.uint8))
     dev[:nb].copy_(host[:nb], non_blocking=True)
     return dev[:nb].view(values.dtype).view(values.shape), triple
 
 
-def _release(triple):
-    from .. import render
-
-    triple[2].record()
-    render._tables.append(triple)
+_release = release_table
 
 
 def window_table(video_ids) -> Tuple[List[int], int]:
@@ -132,8 +127,6 @@ def moments_topk(steds: torch.Tensor, time_mask: Optional[torch.Tensor] = None, 
     video_ids: a host list, equal consecutive ids = the windows of one video, whose positions are concatenated (None: every
     window is a video); nms = (numerator, denominator): a pair whose temporal IoU with an earlier pick is ABOVE that fraction is
     dropped ((1, 1): plain top-k).  One launch; device tensors come back and nothing here synchronises."""
-    from .. import _hip
-
     _check_moment_args(k, nms)
     if not (torch.is_tensor(steds) and steds.is_floating_point() and steds.dim() == 3 and steds.shape[2] == 2 and steds.shape[0] >= 1 and steds.shape[1] >= 1):
         raise ValueError("steds: a float tensor [n_windows, T, 2]")
